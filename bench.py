@@ -3,13 +3,17 @@
 (13 latent frames, S = 226 + 17 550 tokens, 42 layers, batch 2 = [uncond, cond]) + the fused CFG/DDIM update,
 on synthetic latents and random-init weights of that architecture, bf16, everything through libmrag_hip.so.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
+A plain run sets up, warms up, times the K steps and prints the result line; `--dump-outputs DIR` also writes what the last timed step
+computed (DIR/latents.npy, DIR/velocity.npy, float32).  Everything else this script measures -- the CAMA medians and HIP-graph replay,
+the measured ceilings, the 50-step and shipped-configuration clips, the secondary workloads, the CPU baseline -- runs only under `--full`
+(the `--no-*` options trim a `--full` run).
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL over xGMI); the path shards by clip
 (independent units, SURVEY 8e tier 1): each rank denoises its own clip and the ranks' latents are all-gathered
 once at the end of the loop, inside the timed region.  Weak scaling.
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: the joint-sequence flash attention) and
-`cpu_baseline` (the fp32 oracle on a bounded sample, host cores).
+Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: the joint-sequence flash attention, timed inside the steps) and,
+under --full, `cpu_baseline` (the fp32 oracle on a bounded sample, host cores).
 """
 import argparse
 import json
@@ -26,21 +30,26 @@ import torch  # noqa: E402
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--layers", type=int, default=42, help="debug only: the judged workload is 42")
     ap.add_argument("--frames", type=int, default=49, help="debug only: the judged workload is 49")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure everything beside the headline: CAMA median + HIP-graph replay, "
+                    "measured ceilings, the 50-step and shipped-configuration clips, the secondary workloads and the CPU baseline (N = 1; ~90 s more)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as float32 .npy files under DIR (at most 64 MB together): latents.npy (the "
+                         "denoised latents of every clip, gathered over the ranks) and velocity.npy (rank 0's v-prediction, [uncond ; cond])")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ceilings", action="store_true", help="skip the measured ceilings (sustained MFMA probe, device copy, library GEMMs; ~5 s) printed as roofline.ceilings")
     ap.add_argument("--no-e2e", action="store_true", help="skip the measured 50-step end-to-end clip (about 35 s; N = 1 only)")
     ap.add_argument("--no-shipped-config", action="store_true", help="skip the clip of the reference's SHIPPED evaluation configuration (17 frames, 25 DPM steps, guidance 3; ~6 s), "
-                    "which the default run measures after the timed region.  It launches the dominant attention kernel at a second shape (S = 6 976), so it is ALSO skipped "
-                    "whenever a profiler is attached (rocprofv3's preload is detected): `rocprofv3 --stats -- python3 bench.py` then sees that kernel at the roofline shape only "
+                    "which a --full run measures after the timed region.  It launches the dominant attention kernel at a second shape (S = 6 976), so it is ALSO skipped "
+                    "whenever a profiler is attached (rocprofv3's preload is detected): `rocprofv3 --stats -- python3 bench.py --full` then sees that kernel at the roofline shape only "
                     "and its average duration is comparable with `roofline.avg_launch_ms`")
     ap.add_argument("--shipped-config", action="store_true", help="run the shipped-configuration clip even under a profiler (profiles then separate the two shapes by grid size: tools/run_final.sh)")
     ap.add_argument("--e2e-graph", action="store_true", help="also time the 50-step clip with the DiT forward replayed as a HIP graph (+30 s; bit-identical, no faster: the loop is GPU-bound)")
     ap.add_argument("--cooldown", type=float, default=0.0, help="developer knob: idle seconds between the 50-step clip and the secondary workloads (thermal state check)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other BASELINE configs (SVD / DynamiCrafter UNet CFG step, retrieval, CAMA), which are measured "
+    ap.add_argument("--no-secondary", action="store_true", help="skip the other BASELINE configs (SVD / DynamiCrafter UNet CFG step, retrieval, CAMA), which --full measures "
                     "after the timed region at N = 1 (~30 s) and reported under `secondary_workloads`; for profiling runs that should hold only the headline launches")
     ap.add_argument("--shard", choices=["clips", "sequence", "cfg"], default="clips",
                     help="clips (judged default): one clip per rank, weak scaling; sequence: ONE clip, its token sequence sharded over the ranks "
@@ -55,7 +64,10 @@ def parse():
                     "without touching a GPU")
     ap.add_argument("--check", type=str, default=None, metavar="FILE.npy",
                     help="developer check: rank 0 saves its final latents (fp32 .npy) -- tests compare N = 1 with the sharded N > 1 runs")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def build_models(dev, layers, lat_frames):
@@ -306,6 +318,23 @@ def measured_ceilings(dev, seconds: float = 1.0):
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy in float32, at most DUMP_BYTES together.  Should they exceed it, every array is replaced by the
+    same fraction of its flattened elements, a fixed sample (seed 0, ascending indices): two runs with the same arguments still compare element for element"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    frac = min(1.0, (DUMP_BYTES - 4096 * len(arrays)) / total)          # 4 KiB per file for the .npy header
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if frac < 1.0:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False))]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` without a launcher: start one rank per GPU through torch.distributed.run as a CHILD process (this process has
     not touched the GPU and never does) and exit with its status."""
@@ -387,31 +416,32 @@ def main():
     action_emb = pipe.prepare_action_embeddings(ref_videos, None, do_classifier_free_guidance=True, image=image)
     cuda_sync()
     cama_first_ms = (time.perf_counter() - t0) * 1e3
-    runs = []
-    for _ in range(5):                                    # median of five: one eager pass is ~190 launches, and a host hiccup (allocator, GC) in a single run reads as 60 ms
-        t0 = time.perf_counter()
-        action_emb = pipe.prepare_action_embeddings(ref_videos, None, do_classifier_free_guidance=True, image=image)
-        cuda_sync()
-        runs.append((time.perf_counter() - t0) * 1e3)
-    cama_ms = sorted(runs)[len(runs) // 2]
+    cama_ms, cama_graph_ms = None, None
+    if args.full:
+        runs = []
+        for _ in range(5):                                # median of five: one eager pass is ~190 launches, and a host hiccup (allocator, GC) in a single run reads as 60 ms
+            t0 = time.perf_counter()
+            action_emb = pipe.prepare_action_embeddings(ref_videos, None, do_classifier_free_guidance=True, image=image)
+            cuda_sync()
+            runs.append((time.perf_counter() - t0) * 1e3)
+        cama_ms = sorted(runs)[len(runs) // 2]
 
-    # the same as ONE HIP graph replay per clip (cama.GraphedPredict): CAMA is launch-bound when driven eagerly from Python
-    cama_graph_ms = None
-    try:
-        if dry:
-            raise RuntimeError("dry run: no HIP graph")
-        from motionrag_amd.cama import GraphedPredict
-        gp = GraphedPredict(cam, do_classifier_free_guidance=True)
-        batch_ = {"ref_videos": ref_videos, "video": image[:, None].expand(-1, ref_videos.size(2), -1, -1, -1).contiguous()}
-        gp(batch_)
-        cuda_sync()
-        t0 = time.perf_counter()
-        for _ in range(5):
+        # the same as ONE HIP graph replay per clip (cama.GraphedPredict): CAMA is launch-bound when driven eagerly from Python
+        try:
+            if dry:
+                raise RuntimeError("dry run: no HIP graph")
+            from motionrag_amd.cama import GraphedPredict
+            gp = GraphedPredict(cam, do_classifier_free_guidance=True)
+            batch_ = {"ref_videos": ref_videos, "video": image[:, None].expand(-1, ref_videos.size(2), -1, -1, -1).contiguous()}
             gp(batch_)
-        cuda_sync()
-        cama_graph_ms = (time.perf_counter() - t0) / 5 * 1e3
-    except Exception as e:                       # noqa: BLE001 -- reported, never fatal for the headline measurement
-        cama_graph_ms = f"capture failed: {type(e).__name__}: {e}"[:200]
+            cuda_sync()
+            t0 = time.perf_counter()
+            for _ in range(5):
+                gp(batch_)
+            cuda_sync()
+            cama_graph_ms = (time.perf_counter() - t0) / 5 * 1e3
+        except Exception as e:                   # noqa: BLE001 -- reported, never fatal for the headline measurement
+            cama_graph_ms = f"capture failed: {type(e).__name__}: {e}"[:200]
 
     pipe.action_emb = action_emb
     rope_ip = pipe._prepare_rotary_positional_embeddings(lat_frames, 30, 45, dev)
@@ -431,6 +461,7 @@ def main():
             v = dit(latents, prompt_br, timestep[:b], image_rotary_emb=rope_br, image_latents=image_latents, batch=b)
             v = cfgp.gather_branches(v.view(1, *v.shape)).view(2 * b, *v.shape[1:])
         cfg_step_(v, latents, 6.0, *sched.coeffs(t))
+        return v if i == total - 1 else None                                   # the last step's v-prediction (--dump-outputs)
 
     def barrier():
         if use_pg:
@@ -444,18 +475,20 @@ def main():
     ops.KERNEL_TIMING = []
     t0 = time.perf_counter()
     for i in range(args.warmup, total):
-        step(i)
+        v_last = step(i)
     gathered = latents if seq else gather_latents(latents, world, force=use_pg)        # RCCL all-gather of the ranks' clips at the end of the loop (cfg mode: both copies of a pair)
     barrier()
     elapsed = time.perf_counter() - t0
     timing, ops.KERNEL_TIMING = ops.KERNEL_TIMING, None
     assert torch.isfinite(gathered.float()).all(), "non-finite latents"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latents": gathered, "velocity": v_last})
     # the box's measured ceilings, right after the timed region (the part is in the step's power state), rank 0 at N = 1 only
-    ceilings = measured_ceilings(dev) if (world == 1 and not args.no_ceilings and not dry) else None
+    ceilings = measured_ceilings(dev) if (world == 1 and args.full and not args.no_ceilings and not dry) else None
 
     # BASELINE's second metric, MEASURED outside the timed region: one whole clip = CAMA + 50 motion-injected DDIM steps (N = 1 only)
     e2e_sec, e2e_graph_sec = None, None
-    if world == 1 and not args.no_e2e and args.layers == 42 and args.frames == 49 and not dry:
+    if world == 1 and args.full and not args.no_e2e and args.layers == 42 and args.frames == 49 and not dry:
         lat2 = torch.randn(b, lat_frames, 16, 60, 90, generator=g).to(dev, torch.bfloat16)
         lat2_init = lat2.clone()
         cuda_sync()
@@ -487,7 +520,7 @@ def main():
     # the one its README's seconds-per-clip figures were taken on: CAMA + the whole loop, measured (N = 1 only; ~5 s)
     shipped_sec = None
     profiled = profiler_attached()
-    if world == 1 and not args.no_shipped_config and (args.shipped_config or not profiled) and args.layers == 42 and args.frames == 49 and not dry:
+    if world == 1 and args.full and not args.no_shipped_config and (args.shipped_config or not profiled) and args.layers == 42 and args.frames == 49 and not dry:
         try:
             from motionrag_amd.cogvideox import make_scheduler
             gs = torch.Generator().manual_seed(4321)
@@ -509,7 +542,7 @@ def main():
 
     # the other BASELINE.json configs, measured after the timed region and reported beside the headline (N = 1 only; ~20 s)
     secondary = None
-    if world == 1 and not args.no_secondary and not dry:
+    if world == 1 and args.full and not args.no_secondary and not dry:
         if args.cooldown > 0:
             time.sleep(args.cooldown)
         import contextlib
@@ -589,15 +622,15 @@ def main():
             "frames_per_sec_per_gpu": round(value / world, 4),
             "step_tflops_algorithmic": round(step_flops / 1e12, 1),
             "step_tflops_per_sec_per_gpu": round(step_flops / 1e12 / (elapsed / args.steps), 1),
-            "cama_ms": round(cama_ms, 2), "cama_first_call_ms": round(cama_first_ms, 1),
+            "cama_ms": round(cama_ms, 2) if cama_ms is not None else None, "cama_first_call_ms": round(cama_first_ms, 1),
             "cama_hip_graph_ms": round(cama_graph_ms, 3) if isinstance(cama_graph_ms, float) else cama_graph_ms,
-            "e2e_sec_per_clip_50_steps_est": round(cama_ms * 1e-3 + 50 * ms_per_step * 1e-3, 2),
+            "e2e_sec_per_clip_50_steps_est": round(cama_ms * 1e-3 + 50 * ms_per_step * 1e-3, 2) if cama_ms is not None else None,
             "e2e_sec_per_clip_50_steps_measured": round(e2e_sec, 2) if e2e_sec is not None else None,
             "e2e_sec_per_clip_50_steps_hip_graph": round(e2e_graph_sec, 2) if isinstance(e2e_graph_sec, float) else e2e_graph_sec,
             "e2e_sec_per_clip_shipped_config_17f_25_dpm_steps": round(shipped_sec, 2) if isinstance(shipped_sec, float) else None,     # a number or null, never a string
             "shipped_config_skipped_reason": (None if isinstance(shipped_sec, float) else shipped_sec if isinstance(shipped_sec, str) else
-                                              "rocprofv3 tool library injected (--shipped-config forces the clip)" if profiled and not args.no_shipped_config and world == 1 and not args.shipped_config
-                                              else "not requested / N > 1 / reduced model"),
+                                              "rocprofv3 tool library injected (--shipped-config forces the clip)" if profiled and args.full and not args.no_shipped_config and world == 1 and not args.shipped_config
+                                              else "not requested (--full) / N > 1 / reduced model"),
             "process_group": (("gloo" if (one_gpu or dry) else "nccl") + f", world {world}") if use_pg else None,
             "secondary_workloads": secondary,
             "roofline": {"kernel": "attn16_kernel<3,4,3,true> + attn_combine_kernel (joint text+video flash attention on 16x16x32 MFMAs: optimistic sweep without a running max, row sums on the matrix pipe, key-split tail; 48 heads x 64, S=%d, B=2)" % S,
@@ -623,7 +656,7 @@ def main():
             parts["total_s"] = round(parts["denoise_50_steps_s"] + 1e-3 * sum(v for k, v in parts.items() if k.endswith("_ms")), 2)
             out["e2e_sec_per_clip_full_pipeline"] = parts
         except (KeyError, TypeError):
-            out["e2e_sec_per_clip_full_pipeline"] = None      # a stage was not measured in this run (--no-secondary / --no-e2e / N > 1)
+            out["e2e_sec_per_clip_full_pipeline"] = None      # a stage was not measured in this run (no --full / --no-secondary / --no-e2e / N > 1)
         try:     # the other two pipelines at their shipped step counts (configs/{dynamicrafter,svd}/MotionRAG_open.yml): steps x the measured CFG step + the measured VAE decode
             sw = secondary or {}
             out["e2e_sec_per_clip_other_pipelines_from_measured_parts"] = {
@@ -634,7 +667,7 @@ def main():
                                                           + sw["svd_temporal_vae_14x576x1024"]["encode_frame_ms"] + sw["rag_side_encoders_plus_cama"]["cama_predict_from_pixels_ms"]), 2)}
         except (KeyError, TypeError):
             out["e2e_sec_per_clip_other_pipelines_from_measured_parts"] = None
-        if not args.no_cpu_baseline and world == 1 and not dry:          # the CPU baseline is timed on rank 0 at N = 1 only (other ranks would idle in the barrier)
+        if args.full and not args.no_cpu_baseline and world == 1 and not dry:          # the CPU baseline is timed on rank 0 at N = 1 only (other ranks would idle in the barrier)
             dt, fl, cores, what = cpu_baseline_sample()
             full = dt * (step_flops / fl)
             out["cpu_baseline"] = {"value": round(args.frames / full, 6), "unit": "frames/s", "cores": cores, "machine_cores": os.cpu_count(), "kind": "port",

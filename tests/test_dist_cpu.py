@@ -321,3 +321,30 @@ def test_bench_dry_run_rccl_env_report():
     d = json.loads(res.stdout.strip().splitlines()[-1])
     assert d["dry_run_rccl_env"] and d["gpus_requested"] == 8 and "--nproc-per-node=8" in d["launcher_cmd"] and "127.0.0.1" in d["launcher_cmd"]
     assert "HSA_ENABLE_IPC_MODE_LEGACY" in d["required"] and isinstance(d["hsa_enable_ipc_mode_legacy_ok"], bool)
+
+
+def test_bench_dump_outputs_dry_run(tmp_path):
+    """`--dump-outputs DIR`: after the timed steps rank 0 writes the last step's latents and v-prediction as float32 .npy (<= 64 MB together), the same
+    bits from run to run with the same arguments; `--steps` is the number of timed steps the line reports, and a plain run measures nothing beside them"""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    outs = []
+    for tag in ("a", "b"):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run-cpu", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
+        assert res.returncode == 0, res.stderr[-3000:]
+        d = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert d["cama_ms"] is None and d["secondary_workloads"] is None and d["roofline"]["ceilings"] is None and "cpu_baseline" not in d
+        files = sorted(os.listdir(tmp_path / tag))
+        assert files == ["latents.npy", "velocity.npy"], files
+        assert sum(os.path.getsize(tmp_path / tag / f) for f in files) <= 64 << 20
+        outs.append({f: np.load(tmp_path / tag / f) for f in files})
+    lat, vel = outs[0]["latents.npy"], outs[0]["velocity.npy"]
+    assert lat.dtype == np.float32 and lat.shape == (1, 13, 16, 60, 90) and vel.dtype == np.float32 and vel.shape == (2, 13, 16, 60, 90)
+    assert np.isfinite(lat).all() and np.isfinite(vel).all()
+    for f in outs[0]:
+        np.testing.assert_array_equal(outs[0][f], outs[1][f])
