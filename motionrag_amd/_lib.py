@@ -15,7 +15,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_vo
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
-LIB_PATH = os.environ.get("MRAG_HIP_LIB", os.path.join(_HERE, "libmrag_hip.so"))   # env override: A/B builds in tools/
+LIB_PATH = os.path.join(_HERE, "libmrag_hip.so")
 SOURCES = ["api.hip", "gemm_bf16.hip", "attn_flash.hip", "attn16.hip", "attn_fp8.hip", "comm.hip", "norm.hip", "pointwise.hip", "preprocess.hip", "topk.hip", "unet_ops.hip", "cama_seq.hip", "attn_small.hip", "probe.hip"]
 ABI_VERSION = 10
 # per-file flags: the SLP vectoriser packs the softmax row-sum adds into v_pk_add_f32 + shuffles (slower beside MFMAs)
@@ -183,7 +183,7 @@ def binary_stamp(path: str) -> str:
 
 def build(verbose: bool = False) -> str:
     """Compile csrc/*.hip for gfx950 into motionrag_amd/libmrag_hip.so (in-tree; needs no GPU).  Rebuilds whenever the binary's stamp is not
-    the digest of the sources beside it.  MRAG_EXTRA_HIPCC_FLAGS (developer A/B builds, tools/build_variant.sh) is part of the digest."""
+    the digest of the sources beside it.  MRAG_EXTRA_HIPCC_FLAGS (extra hipcc flags, e.g. -DMRAG_DIAG_VMCNT0; see tools/README.md) is part of the digest."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objs = []
     want = source_hash()
@@ -250,14 +250,10 @@ def lib() -> ctypes.CDLL:
         raise HipLibraryMissing(f"{LIB_PATH} has ABI {L.mrag_abi_version()}, expected {ABI_VERSION}: rebuild")
     L.mrag_source_hash.restype = c_char_p
     have = L.mrag_source_hash().decode()
-    if os.environ.get("MRAG_HIP_LIB_ANY_SOURCE"):                            # the explicit override is for tools/ A/B runs of archived variant libraries
-        want = have
-    else:
-        try:
-            want = source_hash()
-        except OSError as e:                                                 # a binary-only install: nothing to compare the stamp with
-            raise HipLibraryMissing(f"{LIB_PATH} carries stamp {have} but the sources it must be checked against are not readable ({e}); "
-                                    "set MRAG_HIP_LIB_ANY_SOURCE=1 to load a library without its sources") from e
+    try:
+        want = source_hash()
+    except OSError as e:                                                     # a binary-only install: nothing to compare the stamp with
+        raise HipLibraryMissing(f"{LIB_PATH} carries stamp {have} but the sources it must be checked against are not readable ({e})") from e
     if have != want:
         raise HipLibraryMissing(f"{LIB_PATH} was built from other sources (stamp {have}, sources beside it {want}): rebuild with "
                                 "`python -m motionrag_amd._lib` -- a stale or variant binary is never loaded silently")

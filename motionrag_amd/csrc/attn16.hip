@@ -34,31 +34,12 @@ constexpr int TILE_BYTES = KVB * 128;
 // LDS: K ring of NS stages, then the V ring
 constexpr float kBig = 16777216.0f;    // lazy-max trigger: a lane's partial row sum of one tile above 2^24
 
-
-// K fragment reads per group of the score MFMAs: 2 (one key block: 8 VGPRs of fragments -- what lets the optimistic sweep's row-sum accumulators fit
-// the 168 VGPRs of three workgroups per CU) or 4 (two key blocks: faster where registers allow, i.e. at QB = 4).  MRAG_ATTN16_KGROUP pins one for A/B builds.
-#ifdef MRAG_ATTN16_KGROUP
-#define KGROUP_OF(QB) MRAG_ATTN16_KGROUP
-#else
-#define KGROUP_OF(QB) ((QB) == 3 ? 2 : 4)
-#endif
 // Wave priority by phase (fast sweep): three workgroups per CU put three waves on every SIMD, each cycling through score MFMAs -> a vector-only block
 // (48 v_exp + 24 v_cvt_pk, ~480 issue cycles) -> P.V MFMAs.  With equal priorities the oldest wave wins the issue port, whatever it is doing; with
 // s_setprio (QK, EXP, PV) = (1, 0, 2) a wave in its exp block yields to waves that have MFMAs to issue, so the matrix pipe is fed first and the
 // exponentials fill the MFMAs' shadow.  Same-box interleaved, inside the denoise step (profiles/r4_attn_step_ab4.txt): 6.38 -> 6.04 ms per launch,
 // 565.6 -> 551.9 ms per step; (1,0,2) = (2,0,3) = (1,0,3) = (2,1,3); exp at the QK level (1,1,2) keeps only a fifth of the gain; exp ABOVE the MFMA
-// phases loses 7 %.  -DMRAG_ATTN16_SETPRIO=0 builds the loop without priorities.
-#ifndef MRAG_ATTN16_SETPRIO
-#define MRAG_ATTN16_SETPRIO 1
-#endif
-#ifndef MRAG_ATTN16_PRIO_QK
-#define MRAG_ATTN16_PRIO_QK 1
-#define MRAG_ATTN16_PRIO_EXP 0
-#define MRAG_ATTN16_PRIO_PV 2
-#endif
-#ifndef MRAG_ATTN16_OPTIMISTIC
-#define MRAG_ATTN16_OPTIMISTIC 1       // 0: every pass in the safe (checked) form -- the round-3 loop, kept buildable for A/B runs (tools/build_variant.sh)
-#endif
+// phases loses 7 %.
 
 struct Lane16 {
   unsigned ka[2];     // LDS byte address (stage 0, key block 0) of this lane's K fragment for k-step 0 / 1
@@ -66,11 +47,12 @@ struct Lane16 {
   int g;
 };
 
-// 8 K fragments of one 64-key tile -> 8 QB score MFMAs, in two groups of 4 reads: one group (16 VGPRs of fragments) is live at a time.
+// 8 K fragments of one 64-key tile -> 8 QB score MFMAs, in two groups of 4 reads: one group (16 VGPRs of fragments) is live at a time -- faster where
+// registers allow, i.e. at QB = 4.  QB = 3 reads groups of 2 (below).
 // (Requesting both groups up front -- 150 -> 168 VGPRs forced -- lost 4 % when it cost the third workgroup per CU; pruned in round 3.)
 template <int OFF, int QB, typename Between>
 __device__ __forceinline__ void qk16(const Lane16& ln, const bf16x8 (&qf)[QB][2], const f32x4 (&negm)[QB], f32x4 (&s)[4][QB], Between between) {
-  if constexpr (KGROUP_OF(QB) == 2) {
+  if constexpr (QB == 3) {
   // one key block (2 fragment reads, 2 QB MFMAs) at a time: 8 VGPRs of K fragments live instead of 16 -- the room the row-sum accumulators of the
   // optimistic sweep need at 168 VGPRs (three workgroups per CU)
 #pragma unroll
@@ -365,9 +347,7 @@ __global__ __launch_bounds__(NW * 64, QB == 3 ? 3 : (QB == 4 ? 2 : 4)) void attn
           }
         }
         if constexpr (FAST) {
-#if MRAG_ATTN16_SETPRIO
-          __builtin_amdgcn_s_setprio(MRAG_ATTN16_PRIO_EXP);
-#endif
+          __builtin_amdgcn_s_setprio(0);   // EXP
           // P = exp2(S') rounded to bf16: nothing else on the vector pipe
 #pragma unroll
           for (int qb = 0; qb < QB; ++qb) {
@@ -415,13 +395,9 @@ __global__ __launch_bounds__(NW * 64, QB == 3 ? 3 : (QB == 4 ? 2 : 4)) void attn
         }
       }
       if constexpr (FAST) {
-#if MRAG_ATTN16_SETPRIO
-        __builtin_amdgcn_s_setprio(MRAG_ATTN16_PRIO_PV);
-#endif
+        __builtin_amdgcn_s_setprio(2);   // PV
         pv16<V_BASE + OFF, QB, true>(ln, pb, o, &lacc);
-#if MRAG_ATTN16_SETPRIO
-        __builtin_amdgcn_s_setprio(MRAG_ATTN16_PRIO_QK);
-#endif
+        __builtin_amdgcn_s_setprio(1);   // QK
       } else {
 #pragma unroll
         for (int qb = 0; qb < QB; ++qb) l[qb] += ps[qb];
@@ -450,7 +426,6 @@ __global__ __launch_bounds__(NW * 64, QB == 3 ? 3 : (QB == 4 ? 2 : 4)) void attn
   };
 
   bool fast_ok = false;
-#if MRAG_ATTN16_OPTIMISTIC
   {
     sweep(std::true_type{});
     bool bad = false;
@@ -462,7 +437,6 @@ __global__ __launch_bounds__(NW * 64, QB == 3 ? 3 : (QB == 4 ? 2 : 4)) void attn
     // fences the LDS between the sweeps (every wave's tail DMAs were retired just above)
     fast_ok = !__syncthreads_or((int)bad);
   }
-#endif
   if (!fast_ok) sweep(std::false_type{});
 
   if (!wave_active) return;
@@ -542,7 +516,7 @@ static int launch16_split(hipStream_t s, AttnP p, const SplitPlan* pl, void* wor
 
 // Workgroup shapes (interleaved A/B on MI355X; round 2: profiles/r2_attn_ab_variants.txt, round 4 with the optimistic sweep: profiles/r4_attn_*_ab.txt):
 //   QB = 3 (shipped): 48 query rows per wave, 4-wave workgroups of 192 rows, THREE per CU (168 VGPRs, 3 waves per SIMD, 48 KB of LDS each);
-//   QB = 4 (-DMRAG_ATTN16_QB=4): 64 rows per wave, 256-row workgroups, TWO per CU (214 VGPRs): 3/4 of the K / V fragment bytes and barriers per FLOP.
+//   QB = 4 (instantiated, not selected by mrag_attn16_qb): 64 rows per wave, 256-row workgroups, TWO per CU (214 VGPRs): 3/4 of the K / V fragment bytes and barriers per FLOP.
 //           5-7 % behind with the checked loop of round 3; with the optimistic sweep 2.6 % ahead in a cold microbenchmark and 1.5 % behind inside
 //           the denoise step (attn_common.h) -- measured in the step, QB = 3 stays.
 // Retired by measurement and pruned: 32 rows per wave in 8-wave workgroups, fragment prefetching at 150 VGPRs (-4 %), 128-key LDS stages (-1 %).

@@ -27,14 +27,8 @@ int mrag_launch_attn_combine(hipStream_t s, const AttnP& p);
 // 4 -> 256-row workgroups, two per CU (214 VGPRs): fewer K / V fragment bytes and barriers per FLOP.  With the optimistic sweep, QB = 4 is 2.6 % AHEAD
 // at S = 17 776 in a cold interleaved microbenchmark (6.05 vs 6.22 ms, profiles/r4_attn_qb4_ab.txt) and 1.5 % BEHIND inside the denoise step, where the
 // chip sits in its sustained power state (6.38 vs 6.28 ms per launch, 562 vs 560 ms per step on one box: profiles/r4_attn_step_ab.txt) -- the step is
-// what ships, so 3 everywhere.  -DMRAG_ATTN16_QB=4 builds the other shape (tools/build_variant.sh) for A/B runs.
-inline int mrag_attn16_qb(int /*Sq*/) {
-#ifdef MRAG_ATTN16_QB
-  return MRAG_ATTN16_QB;
-#else
-  return 3;
-#endif
-}
+// what ships, so 3 everywhere.
+inline int mrag_attn16_qb(int /*Sq*/) { return 3; }
 inline int mrag_attn16_rows(int qb) { return 64 * qb; }
 inline int mrag_attn16_slots(int qb) { return (qb == 3 ? 3 : (qb == 2 ? 4 : 2)) * 256; }
 // attn16.hip: long unmasked sequences (Sq > 128, Skv >= 256) on v_mfma_f32_16x16x32_bf16; returns MRAG_ENOTSUP for shapes it does not take

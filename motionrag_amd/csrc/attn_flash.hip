@@ -29,20 +29,6 @@
 #include <type_traits>
 #include "../../include/mrag_hip.h"
 
-#ifdef MRAG_ATTN_STAMPS
-// diagnostic build only (tools/build_diag.sh): per-phase s_memtime sums of the long-sequence loop; never compiled into the product
-__device__ unsigned long long* g_stamp_buf = nullptr;
-extern "C" int mrag_debug_set_stamp_buffer(void* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_buf), &p, sizeof(p)); }
-#define MRAG_STAMP(T)                                                                  \
-  do {                                                                                 \
-    __builtin_amdgcn_sched_barrier(0);                                                 \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(T)::"memory");           \
-    __builtin_amdgcn_sched_barrier(0);                                                 \
-  } while (0)
-#endif
-
-
-
 #include "attn_common.h"
 
 namespace {
@@ -506,24 +492,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && !HAS_MASK) ? 4 : 1) void attn_
   // re-read clamped rows so the count never changes) + a raw s_barrier: __syncthreads() would drain the queue.
   const int nt = (skv + KVB - 1) / KVB;
   constexpr int D = NS - 1;   // without the half-tile stagger the stage refilled after barrier #t is the one read in iteration t-1
-#ifdef MRAG_ATTN_STAMPS
-  unsigned long long vm_wait = 0, bar_wait = 0;
-#endif
   auto wait_pair = [&]() {   // all but the (D-1) youngest tile pairs of this wave have landed; then rendezvous
-#ifdef MRAG_ATTN_STAMPS
-    unsigned long long w0, w1, w2;
-    MRAG_STAMP(w0);
-#endif
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPW * (D - 1)) : "memory");
-#ifdef MRAG_ATTN_STAMPS
-    MRAG_STAMP(w1);
-#endif
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-#ifdef MRAG_ATTN_STAMPS
-    MRAG_STAMP(w2);
-    vm_wait += w1 - w0; bar_wait += w2 - w1;
-#endif
   };
   {
     // iteration t reads K(t), V(t) from stage t % NS.  Barrier #j guarantees tile j has landed for every wave; after it each
@@ -535,29 +507,14 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && !HAS_MASK) ? 4 : 1) void attn_
 #pragma unroll
     for (int i = 0; i < D; ++i) { issue_k(i, i); issue_v(i, i); }
     if (late) { wait_pair(); issue_k(D % NS, D); issue_v(D % NS, D); }   // barrier #0
-#ifdef MRAG_ATTN_STAMPS
-    unsigned long long acc_t[6] = {0, 0, 0, 0, 0, 0}, ta, tb, tc, td, te, tg;
-#endif
     auto iter = [&](int t, auto split_c, auto stage_c) {
       constexpr int STG = decltype(stage_c)::value;   // ring stage as a compile-time constant, or -1
-#ifdef MRAG_ATTN_STAMPS
-      MRAG_STAMP(ta);
-#endif
       if (!late) wait_pair();   // barrier #t
-#ifdef MRAG_ATTN_STAMPS
-      MRAG_STAMP(tb);
-#endif
       auto early_issue = [&]() {
         if (!late) { issue_k((t + D) % NS, t + D); issue_v((t + D) % NS, t + D); }
       };
       auto mid = [&]() {
-#ifdef MRAG_ATTN_STAMPS
-        MRAG_STAMP(td);
-#endif
         if (late) { wait_pair(); issue_k((t + 1 + D) % NS, t + 1 + D); issue_v((t + 1 + D) % NS, t + 1 + D); }   // barrier #(t+1)
-#ifdef MRAG_ATTN_STAMPS
-        MRAG_STAMP(te);
-#endif
       };
       if (!wave_active) { early_issue(); mid(); return; }
       f32x16 s0, s1;
@@ -565,17 +522,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && !HAS_MASK) ? 4 : 1) void attn_
       if constexpr (STG >= 0) qk_tile_imm8<STG>(ln, qf, r.negm, s0, s1, early_issue);
       else
       qk_tile(smem + (t % NS) * TILE_BYTES, ln, qf, r.negm, s0, s1, early_issue);
-#ifdef MRAG_ATTN_STAMPS
-      MRAG_STAMP(tc);
-#endif
       softmax_tile<HAS_MASK, false>(p, skv, ln, t, nt, qrow_c, s0, s1, s0, s1, r, pb, mid);
       if constexpr (STG >= 0) pv_tile_imm<STG>(ln, pb, r.o0, r.o1);
       else
       pv_tile(smem + V_BASE + (t % NS) * TILE_BYTES, ln, pb, r.o0, r.o1, r.lacc);
-#ifdef MRAG_ATTN_STAMPS
-      MRAG_STAMP(tg);
-      acc_t[0] += tb - ta; acc_t[1] += tc - tb; acc_t[2] += td - tc; acc_t[3] += te - td; acc_t[4] += tg - te; acc_t[5] += tg - ta;
-#endif
         };
     // full unmasked tiles take the per-block pipeline; the ragged last tile (and the masked instantiation) the one-softmax path,
     // in separate loops so that neither path's live state burdens the other
@@ -593,13 +543,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && !HAS_MASK) ? 4 : 1) void attn_
       }
     }
     for (; t < nt; ++t) iter(t, std::false_type{}, RT{});
-#ifdef MRAG_ATTN_STAMPS
-    if (g_stamp_buf && lane == 0 && blockIdx.x < 2048) {
-      for (int k = 0; k < 6; ++k) g_stamp_buf[((long long)blockIdx.x * NW + wave) * 8 + k] = acc_t[k];
-      g_stamp_buf[((long long)blockIdx.x * NW + wave) * 8 + 6] = nt;
-      g_stamp_buf[((long long)blockIdx.x * NW + wave) * 8 + 7] = (vm_wait << 32) | (bar_wait & 0xffffffffull);
-    }
-#endif
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // retire the clamped tail DMAs before the LDS is released
 
@@ -849,11 +792,9 @@ struct IpFoldP {
   float qscale, out_scale;
 };
 
-#ifndef MRAG_IPFOLD_HG
-#define MRAG_IPFOLD_HG 4    // heads whose V^T image a workgroup keeps in LDS (4 KB each); MI355X, DiT shape: 16 -> 196 us, 8 -> 194, 4 -> 185 (more workgroups in flight)
-#endif
+constexpr int IPFOLD_HG = 4;   // heads whose V^T image a workgroup keeps in LDS (4 KB each); MI355X, DiT shape: 16 -> 196 us, 8 -> 194, 4 -> 185 (more workgroups in flight)
 __global__ __launch_bounds__(256) void ip_attn_folded_kernel(const IpFoldP p) {
-  constexpr int HG = MRAG_IPFOLD_HG;                       // heads per block
+  constexpr int HG = IPFOLD_HG;                            // heads per block
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* vt = (bf16_t*)smem;                               // [HG][64 d][4 swizzled chunks of 8 keys]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -954,7 +895,7 @@ extern "C" int mrag_ip_attn_folded_bf16(void* stream, const void* scores, const 
   p.scores = (const bf16_t*)scores; p.v = (const bf16_t*)v; p.o = (bf16_t*)hidden;
   p.rows = (long long)B * S; p.s_ld = scores_ld; p.o_ld = hidden_ld; p.v_bs = v_batch_stride; p.v_ks = v_key_stride; p.rows_per_batch = S;
   p.H = H; p.keys = keys; p.kv_div = kv_batch_div; p.ks = ks; p.qscale = scale * 1.4426950408889634f; p.out_scale = out_scale;
-  constexpr int HG = MRAG_IPFOLD_HG;
+  constexpr int HG = IPFOLD_HG;
   const size_t lds = HG * 64 * 32 * sizeof(bf16_t);
   const long long groups = ((long long)kv_batch_div * S + 63) / 64;
   hipError_t e = hipFuncSetAttribute((const void*)ip_attn_folded_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -966,9 +907,6 @@ extern "C" int mrag_ip_attn_folded_bf16(void* stream, const void* scores, const 
   if (wg_per_cu == 0) {
     int n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)ip_attn_folded_kernel, 256, lds) != hipSuccess || n <= 0) n = 4;
-#ifdef MRAG_IPFOLD_WG8          // developer A/B build: round 5's grid (eight per CU from the LDS size alone)
-    n = (int)(128 * 1024 / lds);
-#endif
     wg_per_cu = n;
   }
   const long long per = (256LL * wg_per_cu) / (((H + HG - 1) / HG) * (long long)(B / kv_batch_div));

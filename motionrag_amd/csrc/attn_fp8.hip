@@ -35,9 +35,6 @@ constexpr int STAGE = 2 * STAGE_K;    // + 8 KB of V8
 constexpr int NS8 = 4;
 constexpr float kPShift = 2.0f;       // P' = 4 P: a re-centred row's 64-key tile sums to at most 256, below the trigger
 constexpr float kBig8 = 448.0f;       // a 64-key row sum of P' at or above e4m3's largest finite value -> some P' may not have been representable: re-centre
-#ifndef MRAG_ATTN8_SETPRIO
-#define MRAG_ATTN8_SETPRIO 1          // wave priority by phase as in attn16.hip (score MFMAs 1, exp / convert block 0, P.V + row-sum MFMAs 2)
-#endif
 
 struct Fp8P {
   AttnP a;
@@ -230,9 +227,7 @@ __global__ __launch_bounds__(512, 4) void attn8_kernel(const Fp8P fp) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) { negm[i] = -m; s0[i] -= delta; s1[i] -= delta; }
       }
-#if MRAG_ATTN8_SETPRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
+      __builtin_amdgcn_s_setprio(0);   // wave priority by phase as in attn16.hip (score MFMAs 1, exp / convert block 0, P.V + row-sum MFMAs 2)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         s0[i] = __builtin_amdgcn_exp2f(s0[i]);
@@ -243,9 +238,7 @@ __global__ __launch_bounds__(512, 4) void attn8_kernel(const Fp8P fp) {
         pb[v] = (int)pack4_fp8(s0[4 * v], s0[4 * v + 1], s0[4 * v + 2], s0[4 * v + 3]);
         pb[4 + v] = (int)pack4_fp8(s1[4 * v], s1[4 * v + 1], s1[4 * v + 2], s1[4 * v + 3]);
       }
-#if MRAG_ATTN8_SETPRIO
       __builtin_amdgcn_s_setprio(2);
-#endif
       // l^T[., q] = ONES . P8^T: every register of lane (q, .) is the sum of the tile's 64 e4m3 values of its query (the values that multiply V below)
       f32x16 zero16;
 #pragma unroll
@@ -255,9 +248,7 @@ __global__ __launch_bounds__(512, 4) void attn8_kernel(const Fp8P fp) {
       const bool blown = !(tile_sum < kBig8);                        // a saturated (or non-finite) P' makes the sum reach 448; a re-centred tile sums to <= 256
       if (__builtin_expect(!__any(blown), 1) || recentre) break;
       recentre = true;
-#if MRAG_ATTN8_SETPRIO
       __builtin_amdgcn_s_setprio(1);
-#endif
     }
     l += tile_sum;
     u32x4 va[2], vb[2];
@@ -269,9 +260,7 @@ __global__ __launch_bounds__(512, 4) void attn8_kernel(const Fp8P fp) {
     const i32x8 vf1 = {(int)vb[0][0], (int)vb[0][1], (int)vb[0][2], (int)vb[0][3], (int)vb[1][0], (int)vb[1][1], (int)vb[1][2], (int)vb[1][3]};
     o0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(vf0, pb, o0, 0, 0, 0, scale_one, 0, scale_one);
     o1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(vf1, pb, o1, 0, 0, 0, scale_one, 0, scale_one);
-#if MRAG_ATTN8_SETPRIO
     __builtin_amdgcn_s_setprio(1);
-#endif
   };
   auto iter = [&](int t, auto stage_c) {
     constexpr int STG = decltype(stage_c)::value;

@@ -29,32 +29,19 @@ inline int gemm(void* s, const void* A, const void* W, const void* bias, void* C
 // few-row kernel's A load, bit-identical) was built for the round-5 review's "fuse dependent steps" item and MEASURED SLOWER: CAMA 1.63 ms per clip with it against
 // 1.50 ms without, same box, interleaved, although it removes 16 of 114 launches (profiles/r6_cama_ln_in_a_load_ab.txt) -- every one of the 64-512 workgroups of a
 // projection recomputes the statistics of its 32 rows (two passes over 64 KB behind a barrier) before its first MFMA, which costs a 250-row problem more than the
-// 6 us LayerNorm launch it saves.  -DMRAG_CAMA_LNA builds the fused sequencer (tools/build_variant.sh); the C-ABI feature stays available and tested.
-inline int ln(void* s, const void* x, void* y, const void* w, const void* b, int64_t rows, int64_t D, float eps, int64_t y_rows_per_batch, int64_t y_batch_stride);
-inline int gemm_ln(void* s, const void* A, const void* lw, const void* lb, float eps, void* scratch, const void* W, void* C, int64_t M, int64_t N, int64_t K, int epi) {
-  mrag_gemm_args g;
-  memset(&g, 0, sizeof(g));
-  g.A = A; g.W = W; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N; g.epilogue = epi;
-  g.a_ln = 1; g.a_ln_gamma = lw; g.a_ln_beta = lb; g.a_ln_eps = eps;
-#ifdef MRAG_CAMA_LNA         // developer A/B build (tools/build_variant.sh): the one-launch form
-  const int rc = mrag_gemm_bf16(s, &g);
-  if (rc != MRAG_ENOTSUP) return rc;
-#else
-  (void)g;
-#endif
-  const int rl = ln(s, A, scratch, lw, lb, M, K, eps, 0, 0);
-  if (rl != 0) return rl;
-  return gemm(s, scratch, W, nullptr, C, M, N, K, epi, nullptr);
-}
-
+// 6 us LayerNorm launch it saves.  The fused sequencer's build switch lives in git history; the C-ABI feature stays available and tested.
 inline int ln(void* s, const void* x, void* y, const void* w, const void* b, int64_t rows, int64_t D, float eps, int64_t y_rows_per_batch = 0,
-              int64_t y_batch_stride = 0);
-inline int ln(void* s, const void* x, void* y, const void* w, const void* b, int64_t rows, int64_t D, float eps, int64_t y_rows_per_batch, int64_t y_batch_stride) {
+              int64_t y_batch_stride = 0) {
   mrag_ln_args a;
   memset(&a, 0, sizeof(a));
   a.x = x; a.y = y; a.gamma = w; a.beta = b; a.rows = rows; a.D = D; a.ldx = D; a.ldy = D; a.eps = eps;
   a.y_rows_per_batch = y_rows_per_batch; a.y_batch_stride = y_batch_stride;
   return mrag_layernorm_bf16(s, &a);
+}
+inline int gemm_ln(void* s, const void* A, const void* lw, const void* lb, float eps, void* scratch, const void* W, void* C, int64_t M, int64_t N, int64_t K, int epi) {
+  const int rl = ln(s, A, scratch, lw, lb, M, K, eps);
+  if (rl != 0) return rl;
+  return gemm(s, scratch, W, nullptr, C, M, N, K, epi, nullptr);
 }
 
 #define TRY(expr)             \

@@ -53,9 +53,6 @@ __device__ __forceinline__ f32x2 gelu_tanh_f2(const f32x2 x) {
 // (|error| <= 0.75e-7, far below a bf16 ulp), used symmetrically:  gelu(x) = x Phi(x) = max(x, 0) - |x| Q(|x|)  -- no copysign, no 1 + erf, no
 // 0.5 x: one v_rcp + one v_exp + 6 FMAs + 5 multiplies / max (13 vector instructions; the 1 - erf form took 16; the branchy libm erff ~40).  In a
 // short-K GEMM (the UNets' K = 320 GEGLU projections) this epilogue is as long as the K loop.  |x| rides as a source modifier.
-#ifndef MRAG_GELU_PACKED
-#define MRAG_GELU_PACKED 0     // 1: the same operations on value PAIRS with v_pk_*_f32 (A/B builds; measured no faster: packed fp32 issues at half rate here)
-#endif
 __device__ __forceinline__ float gelu_erf_f(float x) {
   const float ax = fabsf(x);
   const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(ax, 0.3275911f * 0.7071067811865476f, 1.0f));   // v_rcp_f32 (1 ulp), not the IEEE reciprocal sequence
@@ -67,23 +64,8 @@ __device__ __forceinline__ float gelu_erf_f(float x) {
   const float q = ((pl * t) * e) * ax;                                                                      // |x| Q(|x|)
   return fmaxf(x, 0.0f) - q;
 }
-__device__ __forceinline__ f32x2 gelu_erf_f2(const f32x2 x) {
-#if MRAG_GELU_PACKED
-  const f32x2 ax = {fabsf(x[0]), fabsf(x[1])};
-  const f32x2 den = __builtin_elementwise_fma(ax, f32x2{0.3275911f * 0.7071067811865476f, 0.3275911f * 0.7071067811865476f}, f32x2{1.0f, 1.0f});
-  const f32x2 t = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-  f32x2 pl = __builtin_elementwise_fma(t, f32x2{0.5f * 1.061405429f, 0.5f * 1.061405429f}, f32x2{0.5f * -1.453152027f, 0.5f * -1.453152027f});
-  pl = __builtin_elementwise_fma(pl, t, f32x2{0.5f * 1.421413741f, 0.5f * 1.421413741f});
-  pl = __builtin_elementwise_fma(pl, t, f32x2{0.5f * -0.284496736f, 0.5f * -0.284496736f});
-  pl = __builtin_elementwise_fma(pl, t, f32x2{0.5f * 0.254829592f, 0.5f * 0.254829592f});
-  const f32x2 z = (ax * -0.7213475204444817f) * ax;
-  const f32x2 e = {__builtin_amdgcn_exp2f(z[0]), __builtin_amdgcn_exp2f(z[1])};
-  const f32x2 q = ((pl * t) * e) * ax;
-  return f32x2{fmaxf(x[0], 0.0f), fmaxf(x[1], 0.0f)} - q;
-#else
-  return f32x2{gelu_erf_f(x[0]), gelu_erf_f(x[1])};
-#endif
-}
+// (the same operations on value PAIRS with v_pk_*_f32 measured no faster: packed fp32 issues at half rate here)
+__device__ __forceinline__ f32x2 gelu_erf_f2(const f32x2 x) { return f32x2{gelu_erf_f(x[0]), gelu_erf_f(x[1])}; }
 // GEGLU on four (value, gate) pairs of one lane: v <- bf16(v) * act(bf16(g)) (the reference rounds both halves of proj(x) to bf16 before the product:
 // nn.Linear output dtype); TANH selects the tanh gate (T5's gated-gelu), else the exact-erf one (lvdm attention.py:448-455 / diffusers GEGLU)
 template <bool TANH>

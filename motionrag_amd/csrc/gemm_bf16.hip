@@ -16,38 +16,6 @@
 #include "common.h"
 #include "../../include/mrag_hip.h"
 
-#ifdef MRAG_GEMM_STAMPS
-// diagnostic build only (tools/build_diag.sh): per-phase s_memtime sums of the 256x256 main loop; never compiled into the product
-__device__ unsigned long long* g_gemm_stamp_buf = nullptr;
-extern "C" int mrag_debug_set_gemm_stamp_buffer(void* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_stamp_buf), &p, sizeof(p)); }
-#define MRAG_GSTAMP(T)                                                                 \
-  do {                                                                                 \
-    __builtin_amdgcn_sched_barrier(0);                                                 \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(T)::"memory");           \
-    __builtin_amdgcn_sched_barrier(0);                                                 \
-  } while (0)
-#else
-#define MRAG_GSTAMP(T) do {} while (0)
-#endif
-#ifndef MRAG_W4_RESID_DEPTH
-#define MRAG_W4_RESID_DEPTH 2   // residual row groups in flight in the four-wave kernel's epilogue (developer knob: tools/build_variant.sh)
-#endif
-#ifndef MRAG_GEMM_TRACE
-#define MRAG_GEMM_TRACE 0
-#endif
-#ifdef MRAG_GEMM_SAMEK   // diagnostic only: every K-tile re-reads tile 0 (always L2-resident) to separate memory latency from sync cost
-#define MRAG_DIAG_KSTEP 0
-#else
-#define MRAG_DIAG_KSTEP BK
-#endif
-
-#ifndef MRAG_QK_RING
-#define MRAG_QK_RING 4   // row groups of RoPE table rows in flight in the QKNORM_ROPE epilogue (16 registers each; 6+ spill and lose)
-#endif
-#ifndef MRAG_QK_PRE
-#define MRAG_QK_PRE 0    // of which requested before the accumulators are staged (measured equal to 0 on MI355X: 1.925 vs 1.927 ms)
-#endif
-
 namespace {
 
 struct GemmP {
@@ -222,10 +190,6 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int wg, const in
   static_assert(PIECES % NW == 0, "piece split");
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef MRAG_GEMM_STAMPS
-  unsigned long long g_entry, g_loop0 = 0, g_loop1 = 0, g_exit;
-  MRAG_GSTAMP(g_entry);
-#endif
   const int wm = wave / WN, wn = wave % WN;
 
   // logical tile order: groups of GROUP_M m-tiles walked n-major, so the ~32 workgroups resident on one XCD (a contiguous
@@ -383,7 +347,7 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int wg, const in
   // request piece i of K-tile kt into `dst` (the piece's 1-KiB slot of a stage).  Convolutions: cv_prepare(kt) ran for this K-tile.
   auto dma_piece = [&](int i, int kt, char* dst) {
     if constexpr (CONV == 0) {
-      glds16(gsrc[i] + (long long)kt * MRAG_DIAG_KSTEP, dst);
+      glds16(gsrc[i] + (long long)kt * BK, dst);
     } else if constexpr (!SLIM) {
       glds16(i >= APW ? gsrc[i] + (long long)kt * BK : cv_src[i < APW ? i : 0], dst);      // weight rows [Cout, taps * Cin] are plain
     } else {
@@ -415,9 +379,6 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int wg, const in
     // behind it every wave has finished reading stage t (so the DMA of tile t+2 may overwrite it) and tile t+1 has landed (so
     // the reads of (t+1, 0) are issued right there, under the MFMAs of (t, 1)).  No fragment latency is exposed at the tile
     // boundary (measured before: ~350 cycles of first-fragment wait + ~500 of barrier per 2048-cycle MFMA body).
-#ifdef MRAG_GEMM_STAMPS
-    unsigned long long g_acc[5] = {0, 0, 0, 0, 0}, g0, g1, g2, g3, g4, g5;
-#endif
 #define MRAG_READ12(W, A, AW, AA)                                                                                   \
       asm volatile(                                                                                                  \
           "ds_read_b128 %0, %12 offset:32768\n\tds_read_b128 %1, %12 offset:34816\n\t"                               \
@@ -449,33 +410,17 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int wg, const in
       asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     }
     MRAG_READ12(w0, a0, smem_u + offW + c0, smem_u + offA + c0);
-#ifdef MRAG_GEMM_STAMPS
-    MRAG_GSTAMP(g_loop0);
-#endif
     for (int kt = 0; kt < nk; ++kt) {
-      MRAG_GSTAMP(g0);
       const unsigned st = smem_u + (kt & 1) * STAGE_BYTES;
       MRAG_WAIT12(0, w0, a0);            // the (t, 0) fragments (requested one k-step ago) are here
-      MRAG_GSTAMP(g1);
       MRAG_ROW(0, w0, a0[0]);
       MRAG_READ12(w1, a1, st + offW + c1, st + offA + c1);   // behind the first MFMAs: the 12 KB read burst of 8 waves takes up to ~380 cycles to issue
       MRAG_ROW(1, w0, a0[1]); MRAG_ROW(2, w0, a0[2]); MRAG_ROW(3, w0, a0[3]);
       MRAG_ROW(4, w0, a0[4]); MRAG_ROW(5, w0, a0[5]); MRAG_ROW(6, w0, a0[6]); MRAG_ROW(7, w0, a0[7]);
       __builtin_amdgcn_sched_barrier(0);
       MRAG_WAIT12(0, w1, a1);            // this wave is done reading stage t
-      MRAG_GSTAMP(g2);
       const bool more = kt + 1 < nk, more2 = kt + 2 < nk;
-      if (more) {
-#ifdef MRAG_GEMM_STAMPS
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        MRAG_GSTAMP(g5);
-        g_acc[4] += g5 - g2;
-        asm volatile("s_barrier" ::: "memory");
-#else
-        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");   // tile t+1 landed for every wave; stage t is free
-#endif
-      }
-      MRAG_GSTAMP(g3);
+      if (more) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");   // tile t+1 landed for every wave; stage t is free
       // the 8 LDS-DMA pieces of tile t+2 go into stage t, ONE PER ROW GROUP between the MFMAs (a burst of 8 costs ~100 cycles
       // each at issue, measured with s_memtime stamps)
       char* nbase = smem + (kt & 1) * STAGE_BYTES;
@@ -496,28 +441,10 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int wg, const in
       MRAG_ROW(7, w1, a1[7]); MRAG_PIECE(7);
       __builtin_amdgcn_sched_barrier(0);
 #undef MRAG_PIECE
-#ifdef MRAG_GEMM_STAMPS
-      MRAG_GSTAMP(g4);
-      g_acc[0] += g1 - g0; g_acc[1] += g2 - g1; g_acc[2] += g3 - g2; g_acc[3] += g4 - g3;
-      if (MRAG_GEMM_TRACE && g_gemm_stamp_buf && lane == 0 && blockIdx.x < 4 && kt >= 8 && kt < 12) {   // absolute timeline of 4 K-tiles, after the 64 Ki-word summary
-        unsigned long long* tr = g_gemm_stamp_buf + 65536 + (((long long)blockIdx.x * 8 + wave) * 4 + (kt - 8)) * 8;
-        tr[0] = g0; tr[1] = g1; tr[2] = g2; tr[3] = g5; tr[4] = g3; tr[5] = g4;
-        unsigned hwid; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        tr[6] = hwid;
-      }
-#endif
     }
 #undef MRAG_READ12
 #undef MRAG_WAIT12
 #undef MRAG_ROW
-#ifdef MRAG_GEMM_STAMPS
-    MRAG_GSTAMP(g_loop1);
-    if (g_gemm_stamp_buf && lane == 0 && blockIdx.x < 1024) {
-      for (int k = 0; k < 4; ++k) g_gemm_stamp_buf[((long long)blockIdx.x * 8 + wave) * 8 + k] = g_acc[k];
-      g_gemm_stamp_buf[((long long)blockIdx.x * 8 + wave) * 8 + 4] = nk;
-      g_gemm_stamp_buf[((long long)blockIdx.x * 8 + wave) * 8 + 5] = g_acc[4];
-    }
-#endif
   } else {
     for (int kt = 0; kt < nk; ++kt) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -619,8 +546,9 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int wg, const in
     // inside the per-row `is a video row` branch they serialised 16 global-load latencies per workgroup.  They are fetched UNCONDITIONALLY
     // instead (text rows read table row 0 and discard it) through a ring of QK_RING row groups of registers, each slot refilled as it is
     // consumed.  MI355X, M = 35 552, N = 9216, K = 3072 (interleaved A/B): 1.99-2.01 ms before, 1.925 ms with a ring of 3 or 4; rings of
-    // 5+ make hipcc spill the table registers and lose the gain again.
-    constexpr int QK_RING = MRAG_QK_RING, QK_PRE = MRAG_QK_PRE;
+    // 5+ make hipcc spill the table registers and lose the gain again.  The ring is filled after the accumulators are staged: requesting
+    // the first row groups before that measured equal (1.925 vs 1.927 ms).
+    constexpr int QK_RING = 4;   // row groups in flight, 16 registers each
     f32x4 qk_tab[EPI == MRAG_EPI_QKNORM_ROPE ? QK_RING : 1][4];
     unsigned qk_video = 0;              // bit g: row group g's row lies past the text rows (RoPE applies)
     int qk_which = 2;                   // 0 = Q, 1 = K, 2 = V columns (wave-uniform)
@@ -642,10 +570,6 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int wg, const in
     if constexpr (EPI == MRAG_EPI_QKNORM_ROPE) {
       qk_which = p.qk_first + (int)((bn0 + wn * TN * 16) / p.qk_D);
       has_rope = p.rcos != nullptr && qk_which < 2;
-      if (has_rope) {
-#pragma unroll
-        for (int g = 0; g < QK_PRE; ++g) qk_fetch(g);
-      }
     }
     __syncthreads();   // every wave is done with the operand stages that these per-wave regions overlay
 #pragma unroll
@@ -719,7 +643,7 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int wg, const in
         }
         if (has_rope) {
 #pragma unroll
-          for (int g = QK_PRE; g < QK_RING; ++g) qk_fetch(g);
+          for (int g = 0; g < QK_RING; ++g) qk_fetch(g);
         }
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
@@ -764,14 +688,6 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int wg, const in
         *(u32x2*)(p.C + m * p.ldc + n) = half;
       }
     }
-#ifdef MRAG_GEMM_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    MRAG_GSTAMP(g_exit);
-    if (g_gemm_stamp_buf && lane == 0 && blockIdx.x < 1024) {
-      g_gemm_stamp_buf[((long long)blockIdx.x * 8 + wave) * 8 + 6] = g_loop0 - g_entry;
-      g_gemm_stamp_buf[((long long)blockIdx.x * 8 + wave) * 8 + 7] = g_exit - g_loop1;
-    }
-#endif
     return;
   }
   // ---- the 256x320 tile (TN = 5: 80 columns = 160 bytes per wave row; the UNets' level-0 convolutions and linears, N = 320 / 960): the same staging in two
@@ -1140,7 +1056,7 @@ __device__ __forceinline__ void epilogue_w4(const GemmP& p, char* smem, f32x4 (&
       }
       if (has_rope) { qk_fetch(0); qk_fetch(1); qk_fetch(2); }
     }
-    constexpr int RD = MRAG_W4_RESID_DEPTH;                                               // residual row groups in flight (requested RD - 1 groups ahead of their use; deeper rings measured no faster and cost registers)
+    constexpr int RD = 2;   // residual row groups in flight (requested RD - 1 groups ahead of their use; deeper rings measured no faster and cost registers)
     u32x2 rr[RD][8];
     auto fetch = [&](const int i, const int slot) __attribute__((always_inline)) {
       if constexpr (HAS_R) {
@@ -1423,10 +1339,6 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmP p) {
       MRAG_W4_MF(i, j + 1, w1, a1);
     });
   };
-#ifdef MRAG_GEMM_STAMPS
-  unsigned long long q_acc[6] = {0, 0, 0, 0, 0, 0}, q0, q1, q2, q3, q4, q_in;
-  MRAG_GSTAMP(q_in);
-#endif
   // ---- prologue: the stream's first two K-tiles, the first fragments
   cursor_set(0);
   if (!d_valid) return;
@@ -1444,41 +1356,25 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmP p) {
   for (int r = 0;; ++r) {
     const int L = r * G + slot;
     if (L >= tiles) break;
-    MRAG_GSTAMP(q0);
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     asm volatile("s_nop 4" ::: "memory");   // accumulator writes -> first MFMA (the asm MFMAs are invisible to hipcc's hazard pass)
-    MRAG_GSTAMP(q1);
     for (int t = 0; t < nk; ++t, ++g) {
       kstep(g, !(t == 0 && r > 0));
       advance();
     }
-    MRAG_GSTAMP(q2);
     // the MFMAs above are invisible to hipcc's hazard pass: the accumulators are read (v_accvgpr_read) only after the matrix pipe has drained; every DMA piece
     // in flight (issued BEFORE the stores below) is waited for here, so the next counted wait in the loop comes two K-tiles after the stores
     asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15\n\ts_nop 15\n\ts_nop 7" ::: "memory");
-    MRAG_GSTAMP(q3);
     int tm, tn;
     tile_coords(p, L, tm, tn);
     long long e_bm0, e_mend, e_woff;
     tile_origin(tm, e_bm0, e_mend, e_woff);
     if constexpr (is_geglu<EPI>) epilogue_w4_geglu<EPI>(p, smem, acc, e_bm0, (long long)tn * 256, wave, wm * 128, wn * 128, lane);
     else epilogue_w4<EPI>(p, smem, acc, e_bm0, (long long)tn * 256, wave, wm * 128, wn * 128, lane, e_mend);
-#ifdef MRAG_GEMM_STAMPS
-    MRAG_GSTAMP(q4);
-    q_acc[0] += q1 - q0; q_acc[1] += q2 - q1; q_acc[2] += q3 - q2; q_acc[3] += q4 - q3; q_acc[4] += 1;
-#endif
   }
-#ifdef MRAG_GEMM_STAMPS
-  MRAG_GSTAMP(q4);
-  if (g_gemm_stamp_buf && lane == 0 && blockIdx.x < 1024) {
-    unsigned long long* o = g_gemm_stamp_buf + ((long long)blockIdx.x * 8 + wave) * 8;
-    for (int k = 0; k < 5; ++k) o[k] = q_acc[k];
-    o[5] = q4 - q_in;
-  }
-#endif
 #undef MRAG_W4_MF
 #undef MRAG_W4_RD
 #undef MRAG_W4_LGKM0
@@ -1634,9 +1530,9 @@ __global__ __launch_bounds__(640) void gemm_k320_kernel(const GemmP p) {
     const bool more = tile + G < tiles;
     if (more) {
       issue(tile + G, stage ^ 1);                           // (the other stage was released by the barrier that closed the previous iteration)
-      // INVARIANT of the counted wait (as in topk_mfma_kernel): vmcnt retires in order and counts every vector-memory operation of the wave -- the residual loads and C
-      // stores of the previous tile's epilogue are all issued BEFORE the next tile's four pieces, so "4 outstanding" means exactly those pieces.  No global access may be
-      // moved between `issue` and this wait.  -DMRAG_DIAG_VMCNT0 replaces it by vmcnt(0): the results must not change.
+      // INVARIANT of the counted wait (as in topk.hip): no vector-memory op may be issued between a stage's DMA pieces and their counted wait.  vmcnt retires in
+      // order and counts every vector-memory op of the wave; the previous tile's residual loads and C stores all precede `issue`, so "4 outstanding" means exactly
+      // the next tile's four pieces.  -DMRAG_DIAG_VMCNT0 turns the wait into vmcnt(0): the results must not change.
 #ifdef MRAG_DIAG_VMCNT0
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #else

@@ -4,10 +4,8 @@
 #include "common.h"
 #include "../../include/mrag_hip.h"
 
-#ifndef MRAG_LN_STREAM_WGS
-#define MRAG_LN_STREAM_WGS 2        // persistent workgroups per CU of layernorm_stream_kernel (developer knobs: tools/build_variant.sh).  With the next row prefetched the
-#define MRAG_LN_STREAM_PREFETCH 1   // kernel holds 144 registers of row + per-column vectors: two workgroups per CU
-#endif
+// persistent workgroups per CU of layernorm_stream_kernel: with the next row prefetched the kernel holds 144 registers of row + per-column vectors
+constexpr int LN_STREAM_WGS = 2;
 
 namespace {
 
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const LnP p) {
 // roundings), so the two kernels give the SAME BITS: a sequence-sharded rank (fewer rows: the per-row kernel) reproduces the unsharded model's rows.
 // D = 512 MAXC exactly (every lane busy), no output row remap.
 template <int MAXC>
-__global__ __launch_bounds__(256, MRAG_LN_STREAM_WGS) void layernorm_stream_kernel(const LnP p) {
+__global__ __launch_bounds__(256, LN_STREAM_WGS) void layernorm_stream_kernel(const LnP p) {
   const int lane = threadIdx.x & 63;
   const long long nw = (long long)gridDim.x * 4, gw = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (gw >= p.rows) return;
@@ -140,7 +138,7 @@ __global__ __launch_bounds__(256, MRAG_LN_STREAM_WGS) void layernorm_stream_kern
   for (long long row = gw; row < p.rows; row += nw) {
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) cur[c] = nxt[c];
-    if (MRAG_LN_STREAM_PREFETCH && row + nw < p.rows) load_row(row + nw, nxt);
+    if (row + nw < p.rows) load_row(row + nw, nxt);
     if (p.shift0) {                              // the modulation vectors of this row's (sample, segment)
       const unsigned b = (unsigned)row / (unsigned)p.rows_per_batch, pos = (unsigned)row - b * (unsigned)p.rows_per_batch;
       const bool second = (long long)pos >= p.split;
@@ -197,7 +195,6 @@ __global__ __launch_bounds__(256, MRAG_LN_STREAM_WGS) void layernorm_stream_kern
       }
       __builtin_nontemporal_store(pack8(o), (u32x4*)(y + c * 512));
     }
-    if (!MRAG_LN_STREAM_PREFETCH && row + nw < p.rows) load_row(row + nw, nxt);
   }
 }
 
@@ -350,14 +347,12 @@ extern "C" int mrag_layernorm_bf16(void* stream, const mrag_ln_args* a) {
     MRAG_COUNT(MRAG_K_LAYERNORM_ROWS);
     return MRAG_OK;
   }
-#ifndef MRAG_LN_NO_STREAM
   if (a->D == 3072 && a->rows >= 8192 && p.y_rpb == 0) {       // the DiT's AdaLN LayerNorms: persistent waves, per-column factors in registers
-    MRAG_LAUNCH(layernorm_stream_kernel<6>, dim3(256 * MRAG_LN_STREAM_WGS), block, 0, s, p);
+    MRAG_LAUNCH(layernorm_stream_kernel<6>, dim3(256 * LN_STREAM_WGS), block, 0, s, p);
     MRAG_LAUNCH_CHECK();
     MRAG_COUNT(MRAG_K_LAYERNORM_STREAM);
     return MRAG_OK;
   }
-#endif
   // the row lives in MAXC x 8 registers per lane: the tightest instantiation keeps the most waves in flight (D = 3072: 76 VGPRs and
   // 88-90 us at [35552, 3072] with MAXC = 6 against 100 VGPRs and 112-115 us with MAXC = 8 -- 4.9 TB/s, the device's copy rate)
   if (a->D <= 1024) MRAG_LAUNCH(layernorm_kernel<2>, grid, block, 0, s, p);

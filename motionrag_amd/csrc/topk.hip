@@ -490,15 +490,6 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const TopkP p) {
 //   * per-workgroup lists [query][part][16] leave through the workspace and the merge kernel (LIST = 16) finishes, filter order included.
 __device__ __attribute__((aligned(128))) float g_topk_zero[32];    // source of feature chunks past `dim` (never written)
 
-#ifdef MRAG_TOPK_DIAG_STATS   // developer timing build: [0] selection rounds, [1] cycles inside the selection, [2] cycles in the whole kernel, [3] row blocks (summed over workgroups)
-__device__ unsigned long long g_topk_dbg[4];
-extern "C" int mrag_debug_topk_stats(unsigned long long* out_host, int reset) {
-  hipError_t e = hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_topk_dbg), sizeof(g_topk_dbg));
-  if (e == hipSuccess && reset) { unsigned long long z[4] = {0, 0, 0, 0}; e = hipMemcpyToSymbol(HIP_SYMBOL(g_topk_dbg), z, sizeof(z)); }
-  return (int)e;
-}
-#define MRAG_TSTAMP(T) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(T)::"memory")
-#endif
 struct TopkMP {
   const float* db; const int* group; const float* q; const int* excl; const float* qq;
   unsigned* tau_g;        // [nq] the best k-th distance any workgroup has published for the query, as an order-preserving unsigned key (atomicMin)
@@ -606,9 +597,7 @@ __global__ __launch_bounds__(256 * WN) void topk_mfma_kernel(const TopkMP p) {
     const float* src = i < NTAB ? aptr[i < NTAB ? i : 0] : qptr[i < NTAB ? 0 : i - NTAB];
     src = kk < p.dim ? src + kk : g_topk_zero + chunk * 4;
     char* dst = smem + stage * STAGE + ((i < NTAB ? 0 : RB / 8) + wave + NW * (i < NTAB ? i : i - NTAB)) * 1024;
-#ifndef MRAG_TOPK_DIAG_NODMA  // developer timing build: no operand traffic (the MFMAs run on whatever the LDS holds)
     glds16(src, dst);
-#endif
   };
   auto advance = [&]() {
     if (++d_s == p.nslab) { d_s = 0; ++d_blk; set_rows(d_blk); }
@@ -631,10 +620,6 @@ __global__ __launch_bounds__(256 * WN) void topk_mfma_kernel(const TopkMP p) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
   float xx = 0.f;
-#ifdef MRAG_TOPK_DIAG_STATS
-  unsigned long long dbg_t0, dbg_sel = 0, dbg_rounds = 0, dbg_a, dbg_b;
-  MRAG_TSTAMP(dbg_t0);
-#endif
   const int total = nblk * p.nslab;
   __syncthreads();                                   // lists / thresholds initialised
   // prologue: NST - 1 slabs in flight.  Past the end of the stream `issue` keeps requesting (the cursor clamps to the table's last row and re-reads a slab into a
@@ -643,10 +628,10 @@ __global__ __launch_bounds__(256 * WN) void topk_mfma_kernel(const TopkMP p) {
   for (int i = 0; i < NST - 1; ++i) issue_all(i);
   int s = 0, blk = 0, stg = 0;
   for (int it = 0; it < total; ++it) {
-    // INVARIANT of the counted wait: vmcnt retires in order and counts EVERY vector-memory operation of the wave, so between the LDS-DMA pieces of a slab and the wait
-    // that guards it no other vector-memory operation may be issued -- the group-id loads, the tau_g atomics and the list stores of the selection all sit BEHIND this
-    // wait in program order (they are issued after the pieces they could otherwise be mistaken for).  A later edit that puts a global access in front of it silently lets
-    // the MFMAs read a half-landed stage.  -DMRAG_DIAG_VMCNT0 (tools/build_variant.sh) replaces the counted waits by vmcnt(0): the results must not change.
+    // INVARIANT of the counted wait: no vector-memory op may be issued between a stage's DMA pieces and their counted wait.  vmcnt retires in order and counts EVERY
+    // vector-memory op of the wave, so the group-id loads, the tau_g atomics and the list stores of the selection all sit BEHIND this wait in program order; a later
+    // edit that puts a global access in front of it silently lets the MFMAs read a half-landed stage.  -DMRAG_DIAG_VMCNT0 turns the counted waits into vmcnt(0): the
+    // results must not change.
 #ifdef MRAG_DIAG_VMCNT0
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #else
@@ -681,20 +666,8 @@ __global__ __launch_bounds__(256 * WN) void topk_mfma_kernel(const TopkMP p) {
     if (++s < p.nslab) continue;
     // ---- end of a row block: distances, then the selection rounds
     s = 0;
-#ifdef MRAG_TOPK_DIAG_NOSEL   // developer timing build (tools/topk_variants.sh): the MFMA / DMA stream alone
-#if defined(__HIP_DEVICE_COMPILE__)   // (the accumulators stay live: without a consumer hipcc deletes the MFMAs; the host pass cannot parse the "v" constraint)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) asm volatile("" :: "v"(acc[j]));
-    asm volatile("" :: "v"(xx));
-#endif
-    ++blk;
-    continue;
-#endif
     const long long blk_row0 = row_begin + (long long)blk * RB + wm * 32;
     ++blk;
-#ifdef MRAG_TOPK_DIAG_STATS
-    MRAG_TSTAMP(dbg_a);
-#endif
     if constexpr (METRIC == 0) {
       const float xf = xx + __shfl_xor(xx, 32);      // the two half-row chains, added once (either lane: the same two addends)
       if (h == 0 && wn == 0) xxs[wm * 32 + r32] = xf;   // (the query groups hold the same rows: one writes)
@@ -762,9 +735,6 @@ __global__ __launch_bounds__(256 * WN) void topk_mfma_kernel(const TopkMP p) {
         bsel[j] = pass ? br[j] : -1;
         any |= pass;
       }
-#ifdef MRAG_TOPK_DIAG_STATS
-      ++dbg_rounds;
-#endif
       if (!__syncthreads_or(any ? 1 : 0)) break;
       if (tid < QB) {                                 // the owner of query tid: at most NSLOT insertions into its sorted list
         // the list and the round's candidates come into REGISTERS in two bursts of independent LDS reads; every insertion is then a fixed chain of
@@ -838,17 +808,7 @@ __global__ __launch_bounds__(256 * WN) void topk_mfma_kernel(const TopkMP p) {
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-#ifdef MRAG_TOPK_DIAG_STATS
-    MRAG_TSTAMP(dbg_b);
-    dbg_sel += dbg_b - dbg_a;
-#endif
   }
-#ifdef MRAG_TOPK_DIAG_STATS
-  if (tid == 0) {
-    MRAG_TSTAMP(dbg_b);
-    atomicAdd(&g_topk_dbg[0], dbg_rounds); atomicAdd(&g_topk_dbg[1], dbg_sel); atomicAdd(&g_topk_dbg[2], dbg_b - dbg_t0); atomicAdd(&g_topk_dbg[3], (unsigned long long)nblk);
-  }
-#endif
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ring's last NST - 1 (redundant) slabs must have landed before the workgroup gives its LDS back
   __syncthreads();
   if (tid < QB && q0 + tid < p.nq) {
@@ -880,18 +840,6 @@ __device__ __forceinline__ void store_agent_x4(float* ptr, const f32x4 v) {
 }
 __device__ __forceinline__ float load_agent(const float* ptr) { return __hip_atomic_load(ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-#ifdef MRAG_TOPK_DIAG_STATS   // developer timing build of the one-launch form: sums (and maxima) of phase durations in s_memtime ticks -- tools/topk_diag.py names them
-__device__ unsigned long long g_topk_dense_dbg[24];
-extern "C" int mrag_debug_topk_dense_stats(unsigned long long* out_host, int reset) {
-  hipError_t e = hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_topk_dense_dbg), sizeof(g_topk_dense_dbg));
-  if (e == hipSuccess && reset) { unsigned long long z[24] = {}; e = hipMemcpyToSymbol(HIP_SYMBOL(g_topk_dense_dbg), z, sizeof(z)); }
-  return (int)e;
-}
-#define MRAG_DSTAMP(T) do { if (threadIdx.x == 0) MRAG_TSTAMP(T); } while (0)
-#else
-#define MRAG_DSTAMP(T) do { } while (0)
-#endif
-
 struct TopkDP {
   const float* db; const int* group; const float* q; const int* excl;
   float* dist;            // [nq][ld] first scores
@@ -902,9 +850,7 @@ struct TopkDP {
 };
 
 constexpr int dense_stages(int tiles) { return tiles == 1 ? 2 : 3; }   // 32 queries per workgroup: two 20-KB stages, THREE workgroups per CU (10 000 x 256: 632 workgroups = 2.47 per CU)
-#ifndef MRAG_TOPK_DENSE_SLEEP
-#define MRAG_TOPK_DENSE_SLEEP 32     // x 64 cycles between two looks at the `go` word (~1 us)
-#endif
+constexpr int DENSE_SLEEP = 32;     // x 64 cycles between two looks at the `go` word (~1 us)
 constexpr int DENSE_BUF = 128;      // per-wave compaction buffer of the finishing phase: < 64 left over + <= 64 new candidates per step
 constexpr int DENSE_SCR = ((257 + 4 * DENSE_BUF) * 8 + (2 + 2048 + 2 + 2048) * 4 + 15) / 16 * 16;   // bytes of finishing scratch per 256-thread group: candidates | 2 counters, list of passing groups | the group minima (ld / 32 <= 2 048)
 
@@ -914,8 +860,7 @@ constexpr int DENSE_SCR = ((257 + 4 * DENSE_BUF) * 8 + (2 + 2048 + 2 + 2048) * 4
 // about `keep` runs of 128 bytes out of the query's 40 KB at 10 000 rows -- and ALL of them at once: the passing groups are listed first, then every thread
 // loads its elements of the list (one memory round trip; the first form walked the groups two at a time, a dependent load each: 18 us per query).  The
 // scores at or under the bound (about `keep` again) meet in one LDS array and are ordered by counting ranks.
-__device__ __forceinline__ void dense_select(const TopkDP& p, const int q, const bool store, const int lt, Cand* sh, Cand* bufs, int* ctr, unsigned long long* dacc) {
-  (void)dacc;
+__device__ __forceinline__ void dense_select(const TopkDP& p, const int q, const bool store, const int lt, Cand* sh, Cand* bufs, int* ctr) {
   constexpr int CAP = 4 * DENSE_BUF;
   const int lane = lt & 63, wave = lt >> 6;
   const int ngrp = p.ld >> 5;
@@ -925,9 +870,6 @@ __device__ __forceinline__ void dense_select(const TopkDP& p, const int q, const
   int* glist = ctr + 2;
   float* gsh = (float*)(glist + 2048 + 2);              // [ngrp]: the query's group minima, loaded ONCE by the 256 threads (two loads in flight each)
   Cand inf; inf.d = INFINITY; inf.r = INT_MAX;
-  unsigned long long a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0, a5 = 0;
-  (void)a0; (void)a1; (void)a2; (void)a3; (void)a4; (void)a5;
-  MRAG_DSTAMP(a0);
   if (lt < 2) ctr[lt] = 0;
   // (every wave loading all of the minima for itself -- 8 waves x 128 workgroups x 5 uncached loads on 323 KB, i.e. on a handful of memory channels -- made
   // this first access after the wait 5 us)
@@ -954,17 +896,13 @@ __device__ __forceinline__ void dense_select(const TopkDP& p, const int q, const
     const bool b = v < m.d;
     m.d = b ? v : m.d; m.r = b ? g : m.r;
   }
-  unsigned long long b1 = 0, b2 = 0; (void)b1; (void)b2;
-  MRAG_DSTAMP(b1);
   float thr;
   {
     const int rank = cand_rank(m, 64);
     const unsigned long long bal = __ballot(rank == keep - 1 && m.d < INFINITY);
     thr = bal ? __shfl(m.d, __builtin_ctzll(bal)) : INFINITY;   // (+inf when fewer than `keep` lanes saw a finite score: every finite score passes then)
   }
-  MRAG_DSTAMP(b2);
   __syncthreads();                                      // (the counters are zero; the rank scratch is free again)
-  MRAG_DSTAMP(a1);
   // ---- the groups with a score at or under the bound, listed (any order: the result is the top of a strict total order)
   for (int g = lane + 64 * wave; g < ngrp; g += 256) {
     const float gm = gsh[g];
@@ -978,7 +916,6 @@ __device__ __forceinline__ void dense_select(const TopkDP& p, const int q, const
     }
   }
   __syncthreads();
-  MRAG_DSTAMP(a2);
   const int nel = ctr[0] * 32;
   // ---- their scores: four independent loads per thread and step; the ones at or under the bound are appended to `bufs`
   for (int e0 = 0; e0 < nel; e0 += 1024) {
@@ -1007,7 +944,6 @@ __device__ __forceinline__ void dense_select(const TopkDP& p, const int q, const
     }
   }
   __syncthreads();
-  MRAG_DSTAMP(a3);
   const int ns = ctr[1];
   Cand run = inf;
   if (ns <= CAP) {
@@ -1056,15 +992,7 @@ __device__ __forceinline__ void dense_select(const TopkDP& p, const int q, const
     if (wave == 0)
       for (int w = 1; w < 4; ++w) run = wave_merge_top(run, sh[w * 64 + lane], lane);
   }
-  MRAG_DSTAMP(a4);
   finish_query(p.mp, q, run, sh, lt, store);
-  MRAG_DSTAMP(a5);
-#ifdef MRAG_TOPK_DIAG_STATS   // (accumulated in the caller's registers and flushed at the end of the kernel: an atomic issued here would sit in front of the next vmcnt wait)
-  if (threadIdx.x == 0) {
-    dacc[0] += 1; dacc[1] += a1 - a0; dacc[2] += a2 - a1; dacc[3] += a3 - a2; dacc[4] += a4 - a3; dacc[5] += a5 - a4;
-    dacc[6] = dacc[6] > a5 - a0 ? dacc[6] : a5 - a0; dacc[7] += b1 - a0; dacc[8] += b2 - b1; dacc[9] += a1 - b2;
-  }
-#endif
 }
 
 // QBU = queries a workgroup USES of the 32 TN WN its LDS image holds.  96 of 128 (the eight-wave workgroup whose second query group computes ONE of its two tiles):
@@ -1091,9 +1019,6 @@ __global__ __launch_bounds__(256 * WN, TN * WN == 1 ? 3 : WN == 1 ? 2 : 1) void 
   const bool all_tiles = QBU == QB || (wn * TN + TN) * 32 <= QBU;   // (wave-uniform) this wave's query group computes all of its TN tiles
   const long long row_begin = (long long)part * RB;
   const long long row_end = row_begin + RB < p.n_rows ? row_begin + RB : p.n_rows;
-  unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
-  (void)s0; (void)s1; (void)s2; (void)s3; (void)s4;
-  MRAG_DSTAMP(s0);
 
   int exclv[TN]; bool qok[TN];
 #pragma unroll
@@ -1152,7 +1077,7 @@ __global__ __launch_bounds__(256 * WN, TN * WN == 1 ? 3 : WN == 1 ? 2 : 1) void 
   for (int i = 0; i < NST - 1; ++i) issue_all(i);
   int stg = 0;
   for (int it = 0; it < p.nslab; ++it) {
-    // (the invariant of topk_mfma_kernel's counted wait holds here as well: no other vector-memory operation between a slab's pieces and this wait)
+    // (the invariant of topk_mfma_kernel's counted wait holds here as well: no vector-memory op between a stage's DMA pieces and this wait)
 #ifdef MRAG_DIAG_VMCNT0
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #else
@@ -1198,7 +1123,6 @@ __global__ __launch_bounds__(256 * WN, TN * WN == 1 ? 3 : WN == 1 ? 2 : 1) void 
     }
   }
   (void)all_tiles;
-  MRAG_DSTAMP(s1);
   // ---- first scores of the row block
   if constexpr (METRIC == 0) {
     const float xf = xx + __shfl_xor(xx, 32);          // the two half-row chains, added once (either lane: the same two addends)
@@ -1248,17 +1172,8 @@ __global__ __launch_bounds__(256 * WN, TN * WN == 1 ? 3 : WN == 1 ? 2 : 1) void 
   if (tid < QBU && q0 + tid < p.nq) store_agent_x4(p.gmin + ((long long)(q0 + tid) * (p.ld >> 5) + part * 4), *(const f32x4*)(gml + tid * 4));
   for (int idx = tid; idx < QBU * (RB / 4); idx += NT) {
     const int qn = idx / (RB / 4), c4 = idx % (RB / 4);
-#if defined(MRAG_TOPK_DENSE_DIAG_NOD) && MRAG_TOPK_DENSE_DIAG_NOD == 1     // developer timing builds (results are NOT valid): no score stores / plain (cached) stores
-    (void)qn; (void)c4;
-#elif defined(MRAG_TOPK_DENSE_DIAG_NOD) && MRAG_TOPK_DENSE_DIAG_NOD == 2
-    if (q0 + qn < p.nq) *(f32x4*)(p.dist + (long long)(q0 + qn) * p.ld + row_begin + c4 * 4) = *(const f32x4*)(tile + qn * LD + c4 * 4);
-#else
     if (q0 + qn < p.nq) store_agent_x4(p.dist + (long long)(q0 + qn) * p.ld + row_begin + c4 * 4, *(const f32x4*)(tile + qn * LD + c4 * 4));
-#endif
   }
-#if defined(MRAG_TOPK_DENSE_DIAG) && MRAG_TOPK_DENSE_DIAG == 1   // developer timing build: the stream + the dense stores alone (results are NOT produced)
-  return;
-#endif
   if (p.total == 0) return;                            // the two-launch form: topk_dense_finish_kernel follows (kernel boundary = the hand-over)
   // ---- arrive; wait (bounded) until the grid has arrived; finish the queries of this workgroup's arrival ticket.
   // Words (the workspace's zeroed first 64 bytes, words 8..14): seq | set 0 {arrivals, go, claims} | set 1 {..}.  A call uses set (seq & 1); its last arriver
@@ -1272,25 +1187,17 @@ __global__ __launch_bounds__(256 * WN, TN * WN == 1 ? 3 : WN == 1 ? 2 : 1) void 
   // fetch_add; waiters: relaxed agent loads of `go`, barrier, agent-coherent loads of the scores (store_agent_x4 / load_agent above: no L2-wide fences).
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  MRAG_DSTAMP(s2);
   unsigned seq = 0, ret = 0;                           // (lane 0's)
   unsigned *set = nullptr, *other = nullptr;
   if (tid == 0) {
     seq = __hip_atomic_load(p.sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     set = p.sync + 1 + 3 * (seq & 1u);
     other = p.sync + 1 + 3 * ((seq & 1u) ^ 1u);
-#ifdef MRAG_TOPK_DENSE_FENCES   // developer A/B build: the fences of the textbook hand-off on top of the write-through stores
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     ret = __hip_atomic_fetch_add(set, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     flag[1] = ret & 0xffffu;
     const unsigned ticket = ret & 0xffffu;
     unsigned mode = 0;
     if (ticket + 1u == (unsigned)p.total) {
-#ifdef MRAG_TOPK_DENSE_FENCES
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
-#endif
       mode = (ret >> 16) ? 2u : 1u;
       __hip_atomic_store(other + 0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(other + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1299,58 +1206,33 @@ __global__ __launch_bounds__(256 * WN, TN * WN == 1 ? 3 : WN == 1 ? 2 : 1) void 
       __hip_atomic_store(p.sync, seq + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else {
       for (int spin = 0; spin < p.spin_limit && !mode; ++spin) {
-        __builtin_amdgcn_s_sleep(MRAG_TOPK_DENSE_SLEEP);
+        __builtin_amdgcn_s_sleep(DENSE_SLEEP);
         mode = __hip_atomic_load(set + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       if (!mode) {
         const unsigned r2 = __hip_atomic_fetch_add(set, 0x10000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if ((r2 & 0xffffu) == (unsigned)p.total)
           do {
-            __builtin_amdgcn_s_sleep(MRAG_TOPK_DENSE_SLEEP);
+            __builtin_amdgcn_s_sleep(DENSE_SLEEP);
             mode = __hip_atomic_load(set + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           } while (!mode);
       }
     }
-#ifdef MRAG_TOPK_DENSE_FENCES
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     flag[0] = mode; flag[2] = seq & 1u;
   }
   __syncthreads();
   const unsigned mode = flag[0], ticket = flag[1];
-  MRAG_DSTAMP(s3);
-  unsigned long long dacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  (void)dacc;
   unsigned* claims = p.sync + 1 + 3 * flag[2] + 2;
   __syncthreads();
-#if defined(MRAG_TOPK_DENSE_DIAG) && MRAG_TOPK_DENSE_DIAG == 2   // developer timing build: ... + the grid wait, no finishing phase
-  return;
-#endif
-#ifdef MRAG_TOPK_DIAG_STATS
-#define MRAG_DENSE_FLUSH()                                                                                                                              \
-  if (tid == 0) {                                                                                                                                        \
-    atomicAdd(&g_topk_dense_dbg[0], 1ull); atomicAdd(&g_topk_dense_dbg[1], s1 - s0); atomicAdd(&g_topk_dense_dbg[2], s2 - s1); atomicAdd(&g_topk_dense_dbg[3], s3 - s2); \
-    atomicMax(&g_topk_dense_dbg[4], s1 - s0); atomicMax(&g_topk_dense_dbg[5], s2 - s0); atomicMax(&g_topk_dense_dbg[6], s3 - s0);                     \
-    if (dacc[0]) {                                                                                                                                       \
-      atomicAdd(&g_topk_dense_dbg[8], dacc[0]); atomicAdd(&g_topk_dense_dbg[9], dacc[1]); atomicAdd(&g_topk_dense_dbg[10], dacc[2]); atomicAdd(&g_topk_dense_dbg[11], dacc[3]); \
-      atomicAdd(&g_topk_dense_dbg[12], dacc[4]); atomicAdd(&g_topk_dense_dbg[13], dacc[5]); atomicMax(&g_topk_dense_dbg[14], dacc[6]);                 \
-      atomicAdd(&g_topk_dense_dbg[15], dacc[7]); atomicAdd(&g_topk_dense_dbg[16], dacc[8]); atomicAdd(&g_topk_dense_dbg[17], dacc[9]);                 \
-    }                                                                                                                                                    \
-  }
-#else
-#define MRAG_DENSE_FLUSH()
-#endif
-  if (mode == 0) { MRAG_DENSE_FLUSH(); return; }
+  if (mode == 0) return;
   Cand* sh = (Cand*)(smem + (tid >> 8) * SCR);
   Cand* bufs = sh + 257;
   int* glist = (int*)(bufs + 4 * DENSE_BUF);   // (2 counters + the list)
   if (mode == 1) {
     for (long long idx = ticket; idx * NG < p.nq; idx += p.total) {
       const int q = (int)idx * NG + (tid >> 8);
-      dense_select(p, q < p.nq ? q : p.nq - 1, q < p.nq, tid & 255, sh, bufs, glist, dacc);
+      dense_select(p, q < p.nq ? q : p.nq - 1, q < p.nq, tid & 255, sh, bufs, glist);
     }
-    MRAG_DENSE_FLUSH();
     return;
   }
   for (;;) {
@@ -1360,19 +1242,16 @@ __global__ __launch_bounds__(256 * WN, TN * WN == 1 ? 3 : WN == 1 ? 2 : 1) void 
     __syncthreads();
     if ((long long)claim * NG >= p.nq) break;
     const int q = (int)claim * NG + (tid >> 8);
-    dense_select(p, q < p.nq ? q : p.nq - 1, q < p.nq, tid & 255, sh, bufs, glist, dacc);
+    dense_select(p, q < p.nq ? q : p.nq - 1, q < p.nq, tid & 255, sh, bufs, glist);
   }
-  MRAG_DENSE_FLUSH();
 }
-#undef MRAG_DENSE_FLUSH
 
 // the finishing phase as a launch of its own (a workgroup per query): the dense form of tables whose grid is not resident at once
 __global__ __launch_bounds__(256) void topk_dense_finish_kernel(const TopkDP p) {
   __shared__ __attribute__((aligned(16))) char scr[DENSE_SCR];
   Cand* sh = (Cand*)scr;
   Cand* bufs = sh + 257;
-  unsigned long long dacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  dense_select(p, blockIdx.x, true, threadIdx.x, sh, bufs, (int*)(bufs + 4 * DENSE_BUF), dacc);
+  dense_select(p, blockIdx.x, true, threadIdx.x, sh, bufs, (int*)(bufs + 4 * DENSE_BUF));
 }
 
 // compute units of the current device (the grid wait of the one-launch form is taken only when the runtime's occupancy x this count holds the whole grid)
@@ -1404,11 +1283,6 @@ inline MfmaPlan plan_mfma(long long n_rows, int nq) {
   pl.TN = widest;
   for (int t = 1; t <= widest; t <<= 1)
     if (blocks * ((qtiles + t - 1) / t) <= (t == 1 ? 512 : 256)) { pl.TN = t; break; }
-#ifdef MRAG_TOPK_FORCE_TN   // developer knob (tools/topk_variants.sh): the query tile of every plan
-  pl.TN = 1;
-  for (int t = MRAG_TOPK_FORCE_TN; t >= 1; t >>= 1)
-    if (t <= qtiles) { pl.TN = t; break; }
-#endif
   pl.QB = 32 * pl.TN;
   pl.lds = (size_t)mfma_stages(pl.TN) * (pl.RB + pl.QB) * 128 + (size_t)pl.QB * (17 + 8 + 1) * sizeof(Cand) + 4 * 32 * sizeof(float);
   pl.gy = (nq + pl.QB - 1) / pl.QB;
@@ -1448,11 +1322,7 @@ inline DensePlan plan_dense(long long n_rows, int nq, int dim = 768) {
   // Small tables take the small tiles (4 000 x 256: 256 workgroups of one tile), BASELINE config #1's takes 128 queries per workgroup.  A grid that is not
   // resident at once (two launches, no wait) is priced by its work per CU plus one workgroup's duration (the tail): it takes the small tiles.  The three-tile
   // workgroup (96 of the 128 queries an eight-wave workgroup holds) exists for config #1's size: 632 tiles = 237 x 3 -> 3 per busy CU (75.7 us) instead of 158 x 4 (80.8).
-#ifdef MRAG_TOPK_DENSE_TILE       // developer knob: 11, 21, 22 = TN WN of every plan; 23 = the three-tile workgroup
-  const int cand[1][3] = {{MRAG_TOPK_DENSE_TILE == 23 ? 2 : MRAG_TOPK_DENSE_TILE / 10, MRAG_TOPK_DENSE_TILE == 23 ? 2 : MRAG_TOPK_DENSE_TILE % 10, MRAG_TOPK_DENSE_TILE == 23 ? 3 : 0}};
-#else
   const int cand[4][3] = {{2, 2, 0}, {2, 2, 3}, {2, 1, 0}, {1, 1, 0}};                           // TN, WN, tiles used (0 = all).  (64 queries on EIGHT waves -- TN 1, WN 2 -- measured 3 % behind four waves and was never the rule's choice: not instantiated)
-#endif
   double best = 0;
   bool have = false;
   for (int pass = 0; pass < 2 && !have; ++pass)                                        // pass 0: resident grids; pass 1: any
@@ -1492,12 +1362,8 @@ void plan(long long n_rows, int nq, int* slices, int* rows_per_slice) {
   const int ntq = (nq + QT - 1) / QT;
   // workgroups along the database.  A single query (QT = 1) streams best with 512: two workgroups per CU, ~2 000 rows each at 10^6 rows, and only
   // 2 048 per-wave lists for the last arriver to merge -- 523 us = 5.88 TB/s at 10^6 rows against 627 us with 2 048 slices, 6.60 against 6.23 TB/s
-  // at 4 x 10^6 (256: 4.1 TB/s, 384: 5.2, 768: 5.8; round 4, tools/topk_slices_probe.py).  Query tiles keep 2 048 (1 024 costs them 15 %).
-#ifdef MRAG_TOPK_MAX_SLICES
-  const int MAX_SLICES = MRAG_TOPK_MAX_SLICES;
-#else
+  // at 4 x 10^6 (256: 4.1 TB/s, 384: 5.2, 768: 5.8; round 4).  Query tiles keep 2 048 (1 024 costs them 15 %).
   const int MAX_SLICES = QT == 1 ? 512 : 2048;
-#endif
   const int ROWS = small_db(n_rows, nq) ? 64 : 256;     // rows per workgroup pass (4 waves x 16 or 64 rows; 8 rows per wave measured slower:
                                                         // 34.0 vs 27.5 us at 10 k rows -- the 1 256-list merge of the last arriver then dominates)
   long long tiles = (n_rows + ROWS - 1) / ROWS;

@@ -69,7 +69,6 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GnP p) {
   if (rsub < rpp) {
     const bf16_t* base = p.x + ((long long)n * p.HW) * p.C + c_off + col * 8;
     long long px = px0 + rsub;
-#ifndef MRAG_GN_OLD
     // four pixel rows in flight per thread (the chunk is one contiguous run of the sample: px advances by the rows a pass covers), nontemporal: x is streamed once
     // here; accumulated in the same order as the one-at-a-time loop, so the partial sums keep their bits (round 6: the HBM-bound GroupNorm passes sat at 4.8 TB/s
     // against the 6.0 TB/s of the stream copy, whose sweep -- profiles/r6_copy_probe_sweep.txt -- says: contiguous runs, several loads in flight, nontemporal)
@@ -85,7 +84,6 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GnP p) {
         for (int e = 0; e < 8; ++e) { s[e] += v[e]; q[e] += v[e] * v[e]; }
       }
     }
-#endif
     for (; px < px1; px += rpp) {
       float v[8];
       unpack8(*(const u32x4*)(base + px * p.C), v);
@@ -237,7 +235,6 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GnP p, const float*
     }
     return pack8(v);
   };
-#ifndef MRAG_GN_OLD
   // a workgroup walks CONTIGUOUS runs of 4 x 256 vectors (16 KiB), four nontemporal loads in flight per thread (x is not read again before the residual add at the
   // end of the block; y stays a plain store: the convolution behind it reads it nine times).  Channel vector of a thread's first element of a run by one modulo,
   // then conditional subtracts per unrolled vector and per grid stride of runs (a 64-bit modulo per vector is ~100 instructions against 8 FMAs).
@@ -258,10 +255,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GnP p, const float*
     }
   }
   const long long tail0 = nrun * run;
-#else
-  const long long tail0 = 0;
-#endif
-  // (the vectors behind the last whole run -- or, in the MRAG_GN_OLD developer build, all of them: one vector per thread and grid stride)
+  // (the vectors behind the last whole run: one vector per thread and grid stride)
   const unsigned stride = gridDim.x * 256u, cstep = stride % (unsigned)C8;
   unsigned cv = (unsigned)((tail0 + blockIdx.x * 256u + threadIdx.x) % C8);
   for (long long i = tail0 + (long long)blockIdx.x * 256 + threadIdx.x; i < vecs; i += stride, cv = cv + cstep >= (unsigned)C8 ? cv + cstep - (unsigned)C8 : cv + cstep)

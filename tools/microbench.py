@@ -420,7 +420,7 @@ def r6():
     import ctypes
     from motionrag_amd import _lib
     B, S, H, D = 2, 17776, 48, 3072
-    # (1) AdaLN LayerNorm [35 552, 3 072]: layernorm_stream_kernel (unless the library was built with -DMRAG_LN_NO_STREAM: tools/build_variant.sh)
+    # (1) AdaLN LayerNorm [35 552, 3 072]: layernorm_stream_kernel
     x = torch.randn(B, S, D, device=DEV).to(torch.bfloat16)
     w = torch.ones(D, device=DEV, dtype=torch.bfloat16)
     md = (0.3 * torch.randn(B, 4, D, device=DEV)).to(torch.bfloat16)

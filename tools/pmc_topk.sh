@@ -1,13 +1,10 @@
 # developer tool: matrix-pipe / LDS utilisation of the retrieval fan-out kernel (10^6 x 768 table, 256 queries) from rocprofv3 PMC counters, one counter per pass.
-#   tools/pmc_topk.sh [library]      -> gpurun_out/pmc_topk/summary.json
+#   tools/pmc_topk.sh      (no arguments; writes summary.json beside the per-counter output and prints it)
 export TMPDIR=/tmp
 R=$PWD
-LIBV=${1:-}
 mkdir -p $R/gpurun_out/pmc_topk
 cat > /tmp/topk_once.py <<PY
-import os, sys
-if "$LIBV":
-    os.environ["MRAG_HIP_LIB"] = "$R/$LIBV"; os.environ["MRAG_HIP_LIB_ANY_SOURCE"] = "1"
+import sys
 sys.path.insert(0, "$R")
 import torch
 from motionrag_amd import ops
