@@ -89,6 +89,7 @@ enum mrag_kernel_id {
   MRAG_K_TOPK_DENSE,           /* topk_dense_kernel: the fan-out search in ONE launch (tables whose grid is resident at once: dense first scores, bounded grid wait, claimed finishing) */
   MRAG_K_TOPK_DENSE_FINISH,    /* topk_dense_finish_kernel: the finishing phase as its own launch (tables whose dense grid is not resident at once) */
   MRAG_K_GEMM_SKINNY,          /* gemm_skinny_kernel: M <= 256 (CAMA's latents / encoder tokens, the query embedder): eight waves split K, no LDS ring */
+  MRAG_K_TOPK_RERANK,          /* topk_rerank_kernel: the gathered re-rank (stage 2 of the text-then-image retrieval), one workgroup per query */
   MRAG_K_COUNT
 };
 /* copies min(n, MRAG_K_COUNT) counters into out_host (HOST memory) and returns MRAG_K_COUNT */
@@ -546,6 +547,36 @@ int mrag_topk_f32(void* stream, const float* db, const int32_t* group, int64_t n
                   const float* queries, const int32_t* exclude, int32_t n_queries,
                   int32_t k, int32_t metric,
                   int32_t* out_rows, float* out_dist, void* workspace, int64_t workspace_bytes, int32_t postfilter, int32_t order);
+
+/* ------------------------------------------------------------------------ */
+/* Retrieval, gathered re-rank: every query scores ITS OWN short list of    */
+/* table rows.  Stage 2 of the reference's text-then-image retrieval         */
+/* (`ref_video_type: rag_text_image`): src/data/rag.py:82-130 makes the rows  */
+/* of a text search a temporary table, in rank order, and ranks that table by */
+/* `image_embedding` (no filter, no index: L2); callers                        */
+/* src/data/datamodule.py:239-245 (top_k = (2 n + 3, n)) and :306-315 (the      */
+/* image embeddings come from disk).                                           */
+/*   cand_rows [n_queries, n_cand] int32 (device): query q scores only the     */
+/*     rows cand_rows[q, :].  An entry of -1 (the tail of a short stage-1 list) */
+/*     or outside [0, n_rows) is absent; a row listed twice counts twice.       */
+/*   Distance: the order-1 form above (16 interleaved fmaf chains, butterfly    */
+/*     ^8, ^4, ^2, ^1; "l2" = direct sum of (q - x)^2, "dot" = 1 - chain): a     */
+/*     (query, row) pair gets the same fp32 bits as from the order-1 scan and   */
+/*     from the fan-out form's second scoring, whatever the call shape.         */
+/*   Output [n_queries, k] sorted by (dist asc, POSITION in cand_rows[q, :]     */
+/*     asc) -- the position, not the row number: the temporary table is in      */
+/*     stage-1 rank order.  out_rows = table row, out_pos = that position (may  */
+/*     be NULL), out_dist = distance; missing entries: row -1, position -1,     */
+/*     distance +inf.                                                           */
+/*   1 <= k <= n_cand, else MRAG_EINVAL; n_cand <= 64 and dim % 4 == 0, else     */
+/*   MRAG_ENOTSUP; db and queries 16-byte aligned.  No workspace, no counters,   */
+/*   no allocation: ONE launch (one workgroup per query), capturable in a HIP    */
+/*   graph.                                                                      */
+/* ------------------------------------------------------------------------ */
+int mrag_topk_rerank_f32(void* stream, const float* db, int64_t n_rows, int32_t dim,
+                         const float* queries, int32_t n_queries,
+                         const int32_t* cand_rows, int32_t n_cand, int32_t k, int32_t metric,
+                         int32_t* out_rows, int32_t* out_pos, float* out_dist);
 
 /* ------------------------------------------------------------------------ */
 /* Spatio-temporal UNet denoisers (DynamiCrafter lvdm, SVD): channels-last   */

@@ -330,6 +330,47 @@ __global__ __launch_bounds__(256, QT == 16 ? 3 : 4) void topk_scan_kernel(const 
   }
 }
 
+// The order-1 distance of ONE (query, row) pair on 16 lanes (the second scoring of finish_query and the gathered re-rank, topk_rerank_kernel): lane s16
+// of the 16 runs chain s16 -- features 64 j + 4 s16 + {0, 1, 2, 3} (dim % 4 == 0), j ascending -- and chain16_fold adds the 16 partial sums in the fixed
+// butterfly: bit for bit what the scan kernel gives the pair ("dot": the caller takes 1 - the folded chain).  The loads of twelve steps (all of a 768-d row)
+// are issued together and the chain then runs over registers: as a plain loop every step waited for its own two loads -- twelve memory round trips per
+// candidate, ~10 us of the merge.  (A step past the row loads nothing and adds fmaf(0, 0, acc) = acc: a sum of squares is never -0, and 1 - (+-0) = 1.)
+template <int METRIC>
+__device__ __forceinline__ float chain16_partial(const float* x, const float* qv, const int dim, const int s16) {
+  float acc = 0.f;
+  constexpr int UB = 12;
+  for (int kb = 4 * s16; kb < dim; kb += 64 * UB) {
+    float4 xv[UB], q4[UB];
+#pragma unroll
+    for (int u = 0; u < UB; ++u) {
+      const int k0 = kb + 64 * u;
+      const bool in = k0 < dim;
+      xv[u] = in ? *(const float4*)(x + k0) : float4{0.f, 0.f, 0.f, 0.f};
+      q4[u] = in ? *(const float4*)(qv + k0) : float4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int u = 0; u < UB; ++u) {
+      if constexpr (METRIC == 0) {
+        float df = q4[u].x - xv[u].x; acc = __builtin_fmaf(df, df, acc);
+        df = q4[u].y - xv[u].y; acc = __builtin_fmaf(df, df, acc);
+        df = q4[u].z - xv[u].z; acc = __builtin_fmaf(df, df, acc);
+        df = q4[u].w - xv[u].w; acc = __builtin_fmaf(df, df, acc);
+      } else {
+        acc = __builtin_fmaf(q4[u].x, xv[u].x, acc);
+        acc = __builtin_fmaf(q4[u].y, xv[u].y, acc);
+        acc = __builtin_fmaf(q4[u].z, xv[u].z, acc);
+        acc = __builtin_fmaf(q4[u].w, xv[u].w, acc);
+      }
+    }
+  }
+  return acc;
+}
+// p[l] += p[l ^ 8], ^ 4, ^ 2, ^ 1 across the 16 lanes of a pair (every lane ends with the same bits)
+__device__ __forceinline__ float chain16_fold(float acc) {
+  acc += __shfl_xor(acc, 8); acc += __shfl_xor(acc, 4); acc += __shfl_xor(acc, 2); acc += __shfl_xor(acc, 1);
+  return acc;
+}
+
 // one workgroup (4 waves) per query: merge the per-wave partial lists (each sorted ascending, 64 entries).
 // Phase A bounds the answer: the k-th smallest of the lists' MINIMA is an upper bound of the final k-th distance, so only lists
 // whose minimum does not exceed it can contribute (about k of thousands).  Phase B merges just those.  The result is the
@@ -356,32 +397,8 @@ __device__ __forceinline__ void finish_query(const TopkP& p, const int q, Cand r
     const int c = lt >> 4, s16 = lt & 15;                   // (256 threads: c < 16)
     const Cand cc = sh[c];
     float acc = 0.f;
-    if (cc.r != INT_MAX) {
-      const float* x = p.db + (long long)cc.r * p.dim;
-      const float* qv = p.q + (long long)q * p.dim;
-      // chain s16: features 64 j + 4 s16 + {0, 1, 2, 3} (dim % 4 == 0), j ascending.  The loads of twelve steps (all of a 768-d row) are issued together and the
-      // chain then runs over registers: as a plain loop every step waited for its own two loads -- twelve memory round trips per candidate, ~10 us of the merge.
-      // (A step past the row loads nothing and adds fmaf(0, 0, acc) = acc: the sum of squares is never -0.)
-      constexpr int UB = 12;
-      for (int kb = 4 * s16; kb < p.dim; kb += 64 * UB) {
-        float4 xv[UB], q4[UB];
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-          const int k0 = kb + 64 * u;
-          const bool in = k0 < p.dim;
-          xv[u] = in ? *(const float4*)(x + k0) : float4{0.f, 0.f, 0.f, 0.f};
-          q4[u] = in ? *(const float4*)(qv + k0) : float4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-          float df = q4[u].x - xv[u].x; acc = __builtin_fmaf(df, df, acc);
-          df = q4[u].y - xv[u].y; acc = __builtin_fmaf(df, df, acc);
-          df = q4[u].z - xv[u].z; acc = __builtin_fmaf(df, df, acc);
-          df = q4[u].w - xv[u].w; acc = __builtin_fmaf(df, df, acc);
-        }
-      }
-    }
-    acc += __shfl_xor(acc, 8); acc += __shfl_xor(acc, 4); acc += __shfl_xor(acc, 2); acc += __shfl_xor(acc, 1);   // p[l] += p[l ^ 8], ^ 4, ^ 2, ^ 1
+    if (cc.r != INT_MAX) acc = chain16_partial<0>(p.db + (long long)cc.r * p.dim, p.q + (long long)q * p.dim, p.dim, s16);
+    acc = chain16_fold(acc);
     __syncthreads();
     if (s16 == 0 && cc.r != INT_MAX) sh[c].d = acc;
     __syncthreads();
@@ -1533,5 +1550,78 @@ extern "C" int mrag_topk_f32(void* stream, const float* db, const int32_t* group
   MRAG_LAUNCH(topk_merge_kernel<64>, dim3(n_queries), dim3(256), 0, s, p);
   MRAG_LAUNCH_CHECK();
   MRAG_COUNT(MRAG_K_TOPK_MERGE);
+  return MRAG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- gathered re-rank: every query scores ITS OWN short list of rows
+// Stage 2 of the reference's text-then-image retrieval (src/data/rag.py:101-130: the rows of a text search become a temporary table, in rank order, that an
+// image search then ranks; caller src/data/datamodule.py:239-245 with top_k = (2 n + 3, n)).  One 256-thread workgroup per query: 16 lanes per candidate, 16
+// candidates per pass (<= 4 passes), distances in the order-1 form (chain16_partial / chain16_fold: the bits the scan kernel gives the pair), parked in LDS;
+// the first wave then ranks the <= 64 (distance, POSITION in the list) pairs by counting and writes the first k.  An entry outside [0, n_rows) is absent.
+// ~22 MB of rows at 256 x 21 x 1 024 floats: launch- and latency-bound, no pipeline.
+namespace {
+
+struct RerankP {
+  const float* db; const float* q; const int* cand; int* out_rows; int* out_pos; float* out_dist;
+  long long n_rows; int dim, n_cand, k;
+};
+
+template <int METRIC>
+__global__ __launch_bounds__(256) void topk_rerank_kernel(const RerankP p) {
+  __shared__ float sd[64];
+  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int c16 = tid >> 4, s16 = tid & 15;
+  const float* qv = p.q + (long long)q * p.dim;
+  const int* cr = p.cand + (long long)q * p.n_cand;
+  for (int base = 0; base < p.n_cand; base += 16) {
+    const int pos = base + c16;
+    const int row = pos < p.n_cand ? cr[pos] : -1;
+    const bool have = row >= 0 && row < p.n_rows;
+    float acc = 0.f;
+    if (have) acc = chain16_partial<METRIC>(p.db + (long long)row * p.dim, qv, p.dim, s16);
+    acc = chain16_fold(acc);
+    if (s16 == 0 && have) sd[pos] = METRIC == 0 ? acc : 1.0f - acc;
+  }
+  __syncthreads();
+  if (tid >= 64) return;
+  const int row = lane < p.n_cand ? cr[lane] : -1;
+  const bool have = row >= 0 && row < p.n_rows;
+  Cand c;
+  c.d = have ? sd[lane] : INFINITY;
+  c.r = have ? lane : INT_MAX;                               // the tie rule: position in the list, not the row number
+  const int rank = cand_rank(c, p.n_cand);                   // distinct positions -> distinct ranks among the present entries
+  const int found = __popcll(__ballot(have));
+  const long long o = (long long)q * p.k;
+  if (have && rank < p.k) {
+    p.out_rows[o + rank] = row;
+    if (p.out_pos) p.out_pos[o + rank] = lane;
+    p.out_dist[o + rank] = c.d;
+  }
+  if (lane >= found && lane < p.k) {
+    p.out_rows[o + lane] = -1;
+    if (p.out_pos) p.out_pos[o + lane] = -1;
+    p.out_dist[o + lane] = INFINITY;
+  }
+}
+
+}  // namespace
+
+extern "C" int mrag_topk_rerank_f32(void* stream, const float* db, int64_t n_rows, int32_t dim, const float* queries, int32_t n_queries,
+                                    const int32_t* cand_rows, int32_t n_cand, int32_t k, int32_t metric, int32_t* out_rows, int32_t* out_pos,
+                                    float* out_dist) {
+  if (!db || !queries || !cand_rows || !out_rows || !out_dist) return MRAG_EINVAL;
+  if (n_rows <= 0 || n_rows > INT_MAX - 1 || n_queries <= 0 || dim <= 0) return MRAG_EINVAL;
+  if (metric != 0 && metric != 1) return MRAG_EINVAL;
+  if (k <= 0 || n_cand <= 0 || k > n_cand) return MRAG_EINVAL;
+  if (n_cand > 64 || dim % 4 != 0) return MRAG_ENOTSUP;
+  if (((uintptr_t)db | (uintptr_t)queries) & 15) return MRAG_EINVAL;
+  RerankP p{};
+  p.db = db; p.q = queries; p.cand = cand_rows; p.out_rows = out_rows; p.out_pos = out_pos; p.out_dist = out_dist;
+  p.n_rows = n_rows; p.dim = dim; p.n_cand = n_cand; p.k = k;
+  hipStream_t s = (hipStream_t)stream;
+  if (metric == 0) MRAG_LAUNCH(topk_rerank_kernel<0>, dim3(n_queries), dim3(256), 0, s, p);
+  else MRAG_LAUNCH(topk_rerank_kernel<1>, dim3(n_queries), dim3(256), 0, s, p);
+  MRAG_LAUNCH_CHECK();
+  MRAG_COUNT(MRAG_K_TOPK_RERANK);
   return MRAG_OK;
 }

@@ -657,6 +657,33 @@ def topk(db: torch.Tensor, queries: torch.Tensor, k: int, *, metric: str = "l2",
     return rows, dist
 
 
+def topk_rerank(db: torch.Tensor, queries: torch.Tensor, cand_rows: torch.Tensor, k: int, *, metric: str = "l2", out: Optional[tuple] = None):
+    """gathered top-k (mrag_topk_rerank_f32): query q ranks only the table rows `cand_rows[q, :]` (int32 [Q, n_cand], n_cand <= 64; -1 or out of range =
+    absent).  Returns (rows int32 [Q, k], pos int32 [Q, k], dist fp32 [Q, k]) sorted by (dist asc, position in `cand_rows[q, :]` asc); missing entries are
+    row -1, position -1, distance +inf.  Distances are the "chain16" order's bits.  `out` = (rows, pos, dist) buffers to fill.  One launch, no workspace."""
+    _dev(db, torch.float32, "db"); _dev(queries, torch.float32, "queries"); _dev(cand_rows, torch.int32, "cand_rows")
+    if not db.is_contiguous() or not queries.is_contiguous() or not cand_rows.is_contiguous():
+        raise ValueError("topk_rerank: contiguous db / queries / cand_rows required")
+    if db.dim() != 2 or queries.dim() != 2 or cand_rows.dim() != 2 or queries.shape[1] != db.shape[1] or cand_rows.shape[0] != queries.shape[0]:
+        raise ValueError("topk_rerank: db [N, D], queries [Q, D], cand_rows [Q, n_cand]")
+    N, D = db.shape
+    Q, C = cand_rows.shape
+    if not (1 <= k <= C <= 64):
+        raise ValueError(f"topk_rerank: 1 <= k <= n_cand <= 64 (got k = {k}, n_cand = {C})")
+    m = {"l2": 0, "dot": 1}[metric]
+    if out is None:
+        rows = torch.empty(Q, k, dtype=torch.int32, device=db.device)
+        pos = torch.empty(Q, k, dtype=torch.int32, device=db.device)
+        dist = torch.empty(Q, k, dtype=torch.float32, device=db.device)
+    else:
+        rows, pos, dist = out
+        if any(tuple(t.shape) != (Q, k) or not t.is_cuda or not t.is_contiguous() for t in (rows, pos, dist)) or rows.dtype != torch.int32 \
+                or pos.dtype != torch.int32 or dist.dtype != torch.float32:
+            raise ValueError("topk_rerank: out = (int32 [Q, k], int32 [Q, k], float32 [Q, k]) on the device")
+    check(_lib.lib().mrag_topk_rerank_f32(_stream(), _p(db), N, D, _p(queries), Q, _p(cand_rows), C, k, m, _p(rows), _p(pos), _p(dist)), "mrag_topk_rerank_f32")
+    return rows, pos, dist
+
+
 class TopkPlan:
     """A prepared search over a resident database: every buffer (query tile, exclusion ids, workspace, outputs) is allocated once and every
     ctypes argument is built once, so a query costs ONE C-ABI call -- for <= 4 queries one kernel launch (scan + merge fused) -- and nothing is
