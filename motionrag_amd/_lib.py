@@ -11,12 +11,16 @@ import ctypes
 import os
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libmrag_hip.so")
-SOURCES = ["api.hip", "gemm_bf16.hip", "attn_flash.hip", "attn16.hip", "attn_fp8.hip", "comm.hip", "norm.hip", "pointwise.hip", "preprocess.hip", "topk.hip", "unet_ops.hip", "cama_seq.hip", "attn_small.hip", "probe.hip"]
+# compiled in this order, at most MAX_COMPILERS at a time: the long units first, so that none of them starts late behind the short ones
+SOURCES = ["topk.hip", "gemm_tiled.hip", "gemm_w4.hip", "gemm_conv.hip", "attn16.hip", "attn_flash.hip", "gemm_skinny.hip", "api.hip", "gemm_bf16.hip", "gemm_k320.hip", "attn_fp8.hip", "comm.hip", "norm.hip",
+           "pointwise.hip", "preprocess.hip", "unet_ops.hip", "cama_seq.hip", "attn_small.hip", "probe.hip"]
+MAX_COMPILERS = 16
 ABI_VERSION = 11
 # per-file flags: the SLP vectoriser packs the softmax row-sum adds into v_pk_add_f32 + shuffles (slower beside MFMAs)
 EXTRA_FLAGS = {"attn_flash.hip": ["-fno-slp-vectorize"],
@@ -197,7 +201,7 @@ def build(verbose: bool = False) -> str:
     for f in sorted(f for f in os.listdir(_CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "mrag_hip.h")]:
         with open(os.path.join(_CSRC, f), "rb") as fh:
             hdr.update(fh.read())
-    procs = []
+    jobs = []
     for src in SOURCES:
         obj = os.path.join(build_dir, src.replace(".hip", ".o"))
         cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment"] + EXTRA_FLAGS.get(src, []) + extra + (
@@ -213,15 +217,18 @@ def build(verbose: bool = False) -> str:
             print(" ".join(cmd), file=sys.stderr)
         if os.path.exists(tag):
             os.remove(tag)
-        procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT), tag, key))
-    failed = []
-    for src, pr, tag, key in procs:
-        out, _ = pr.communicate()
-        if pr.returncode != 0:
-            failed.append(f"hipcc failed on {src}:\n{out.decode()}")
-        else:
-            with open(tag, "w") as fh:
-                fh.write(key)
+        jobs.append((src, cmd, tag, key))
+
+    def compile_one(job):
+        src, cmd, tag, key = job
+        res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+        if res.returncode != 0:
+            return f"hipcc failed on {src}:\n{res.stdout.decode()}"
+        with open(tag, "w") as fh:
+            fh.write(key)
+
+    with ThreadPoolExecutor(max_workers=MAX_COMPILERS) as pool:       # (started in SOURCES order)
+        failed = [err for err in pool.map(compile_one, jobs) if err]
     if failed:
         raise RuntimeError("\n".join(failed))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs + ["-ldl"]

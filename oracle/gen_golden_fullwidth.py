@@ -4,7 +4,7 @@ Golden vectors from the REFERENCE'S OWN classes at the widths and row counts at 
 the persistent four-wave GEMM (`gemm_w4_kernel`, incl. the fused qk-LayerNorm + RoPE and GEGLU epilogues), `attn16_kernel`,
 `ip_attn_folded_kernel`, the 256x320 tile and the implicit-GEMM convolutions on 256-row tiles -- not the 128x128 fallback tile, the separate
 `qknorm_rope` pass and `attn_flash` that the reduced-width fixtures of gen_golden.py / gen_golden_attn_processor.py reach
-(mrag_gemm_bf16 takes the big tiles from 192 tiles of 256x256 up, csrc/gemm_bf16.hip; attn16 from Sq > 128, Skv >= 256, csrc/attn16.hip).
+(mrag_gemm_bf16 takes the big tiles from 192 tiles of 256x256 up, csrc/gemm_bf16.hip: the dispatch; attn16 from Sq > 128, Skv >= 256, csrc/attn16.hip).
 
     python -m oracle.gen_golden_fullwidth            # writes tests/golden/fullwidth_{cog,svd,dc}.npz
 
