@@ -19,7 +19,8 @@
  *     on the launch path: workspaces are passed in, developer tuning knobs are
  *     explicit `tuning` fields of the argument structs (0 = the shipped
  *     behaviour).  The ONE piece of process-wide state is a table of
- *     diagnostic launch counters (mrag_dispatch_counts) that nothing reads back;
+ *     diagnostic launch counters (mrag_dispatch_counts, mrag_fp8_launch_counts)
+ *     that nothing reads back;
  *   - row-major, innermost dimension contiguous; ld* / stride* are in ELEMENTS.
  */
 #ifndef MRAG_HIP_H
@@ -204,6 +205,45 @@ enum { MRAG_GEMM_TUNE_NO_WIDE = 1, MRAG_GEMM_TUNE_NO_STAGED = 2, MRAG_GEMM_TUNE_
 int mrag_gemm_bf16(void* stream, const mrag_gemm_args* args);
 /* scratch bytes that let mrag_gemm_bf16 run its last, partial round of tiles as stream-K; 0 when the shape has nothing to gain */
 int64_t mrag_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
+
+/* ------------------------------------------------------------------------ */
+/* fp8 (OCP e4m3fn) linear -- OPT-IN, beside the fp8 attention: the DiT's four */
+/* large linears, to_q/to_k/to_v and to_out (attn_processor.py:209-211,276)    */
+/* and the two FeedForward projections of diffusers' CogVideoXBlock, on the    */
+/* block-scaled e4m3 MFMA (twice the bf16 matrix rate).  Nothing takes this     */
+/* path unless asked (cogvideox.set_linear_precision).                         */
+/* ------------------------------------------------------------------------ */
+/* Row quantiser (activations in front of every fp8 GEMM: attn_processor.py:209-211,276 and the CogVideoXBlock FF inputs; weights once, [N, K] rows =
+ * output channels).  x [M, K] bf16 with row stride ldx -> x8 [M, K] e4m3fn bytes with row stride ld8 (bytes) and exp [M]:
+ *   exp[m] = the largest e with max|x[m, :]| * 2^e <= 448, clamped to +-60, 0 for an all-zero row;   x8[m, k] = round-to-nearest-even(x[m, k] * 2^exp[m])
+ * (nothing exceeds 448 under that scale: no saturation).  One pass over x.  MRAG_ENOTSUP unless K % 16 == 0 and the rows of x and x8 are 16-byte
+ * aligned (ldx % 8 == 0, ld8 % 16 == 0, both base pointers 16-byte aligned).                                                                        */
+int mrag_quant_rows_e4m3(void* stream, const void* x, void* x8, int32_t* exp, int64_t M, int64_t K, int64_t ldx, int64_t ld8);
+
+/* C[m, n] = epilogue( 2^-(a_exp[m] + w_exp[n]) * sum_k A8[m, k] * W8[n, k] + bias[n] ): fp32 accumulation in ascending 64-deep MFMA steps, the row
+ * exponents applied inside the MFMA (E8M0 scale operands: exact).  Epilogues MRAG_EPI_NONE, MRAG_EPI_GELU_TANH, MRAG_EPI_RESID and
+ * MRAG_EPI_GATE_RESID with the semantics, the row-range fields and the rounding points of the bf16 GEMM's (the gated / plain projection is rounded to
+ * bf16 before the residual add); C may alias resid.  MRAG_ENOTSUP unless K % 128 == 0 and N % 16 == 0 (any M >= 1) and for every other epilogue;
+ * MRAG_EINVAL for null or misaligned pointers (16-byte aligned rows of A8, W8, C and resid; 8-byte aligned bias and gates).                       */
+typedef struct mrag_gemm_fp8_args {
+  const void* A8;          /* [M, K] e4m3fn bytes, lda (bytes)                   */
+  const void* W8;          /* [N, K] e4m3fn bytes, ldw (nn.Linear weight layout) */
+  const int32_t* a_exp;    /* [M]: A8[m, :] = A[m, :] * 2^a_exp[m]               */
+  const int32_t* w_exp;    /* [N]                                                */
+  const void* bias;        /* [N] bf16 or NULL                                   */
+  void* C;                 /* [M, N] bf16, ldc                                   */
+  const void* resid;       /* [M, N] bf16, ldr (EPI_RESID / EPI_GATE_RESID)      */
+  const void* gate0;       /* EPI_GATE_RESID: as in mrag_gemm_args               */
+  const void* gate1;
+  int64_t M, N, K;
+  int64_t lda, ldw, ldc, ldr;
+  int64_t rows_per_batch, split, gate_stride;
+  int32_t epilogue;        /* enum mrag_epilogue */
+} mrag_gemm_fp8_args;
+int mrag_gemm_fp8(void* stream, const mrag_gemm_fp8_args* args);
+/* host-side relaxed launch counters of the two entry points above (slot 0: GEMM launches, slot 1: quantiser launches), beside the dispatch table
+ * whose enumerators are pinned: copies min(n, 2) of them into out_host (HOST memory) and returns 2.  Tests prove with them that the fp8 kernel ran. */
+int mrag_fp8_launch_counts(uint64_t* out_host, int32_t n);
 
 /* ------------------------------------------------------------------------ */
 /* Attention, head_dim 64, bf16, flash-style (no S x S matrix in HBM).       */

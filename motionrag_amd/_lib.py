@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libmrag_hip.so")
 # compiled in this order, at most MAX_COMPILERS at a time: the long units first, so that none of them starts late behind the short ones
-SOURCES = ["topk.hip", "gemm_tiled.hip", "gemm_w4.hip", "gemm_conv.hip", "attn16.hip", "attn_flash.hip", "gemm_skinny.hip", "api.hip", "gemm_bf16.hip", "gemm_k320.hip", "attn_fp8.hip", "comm.hip", "norm.hip",
+SOURCES = ["topk.hip", "gemm_tiled.hip", "gemm_w4.hip", "gemm_conv.hip", "attn16.hip", "attn_flash.hip", "gemm_skinny.hip", "gemm_fp8.hip", "api.hip", "gemm_bf16.hip", "gemm_k320.hip", "attn_fp8.hip", "comm.hip", "norm.hip",
            "pointwise.hip", "preprocess.hip", "unet_ops.hip", "cama_seq.hip", "attn_small.hip", "probe.hip"]
 MAX_COMPILERS = 16
 ABI_VERSION = 11
@@ -36,6 +36,7 @@ SYMBOLS = [
     "mrag_comm_unique_id", "mrag_comm_init", "mrag_comm_destroy", "mrag_allgather",
     "mrag_resize_patchify_bf16", "mrag_assemble_tokens_bf16", "mrag_softmax_rows_bf16", "mrag_denormalize_u8", "mrag_attn_small_bf16", "mrag_blend_tile_bf16", "mrag_cfg_dpm_step_bf16",
     "mrag_resampler_workspace_bytes", "mrag_resampler_fwd", "mrag_cama_encoder_workspace_bytes", "mrag_cama_encoder_fwd",
+    "mrag_quant_rows_e4m3", "mrag_gemm_fp8", "mrag_fp8_launch_counts",
 ]
 
 
@@ -60,6 +61,17 @@ class GemmArgs(Structure):
         ("qk_dmodel", c_int64), ("qk_eps", c_float), ("q_premul", c_float), ("qk_first", c_int32), ("tuning", c_int32), ("geglu_act", c_int32),
         ("workspace", c_void_p), ("acc_scale", c_float), ("workspace_bytes", c_int64), ("w_batch_stride", c_int64),
         ("a_ln_gamma", c_void_p), ("a_ln_beta", c_void_p), ("a_ln_eps", c_float), ("a_ln", c_int32),
+    ]
+
+
+class GemmFp8Args(Structure):
+    _fields_ = [
+        ("A8", c_void_p), ("W8", c_void_p), ("a_exp", c_void_p), ("w_exp", c_void_p), ("bias", c_void_p), ("C", c_void_p), ("resid", c_void_p),
+        ("gate0", c_void_p), ("gate1", c_void_p),
+        ("M", c_int64), ("N", c_int64), ("K", c_int64),
+        ("lda", c_int64), ("ldw", c_int64), ("ldc", c_int64), ("ldr", c_int64),
+        ("rows_per_batch", c_int64), ("split", c_int64), ("gate_stride", c_int64),
+        ("epilogue", c_int32),
     ]
 
 
@@ -276,6 +288,9 @@ def lib() -> ctypes.CDLL:
     L.mrag_probe_stream_copy.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int32]
     L.mrag_gemm_bf16.argtypes = [c_void_p, POINTER(GemmArgs)]
     L.mrag_attn_fwd_bf16.argtypes = [c_void_p, POINTER(AttnArgs)]
+    L.mrag_quant_rows_e4m3.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64]
+    L.mrag_gemm_fp8.argtypes = [c_void_p, POINTER(GemmFp8Args)]
+    L.mrag_fp8_launch_counts.argtypes = [c_void_p, c_int32]
     L.mrag_gemm_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
     L.mrag_gemm_workspace_bytes.restype = c_int64
     L.mrag_attn_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]

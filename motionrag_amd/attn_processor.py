@@ -101,11 +101,14 @@ class _FusedWeights:
         self._cache.clear()
 
 
-def joint_attention_core(attn, proc, x: torch.Tensor, text_len: int, rope, ip_hidden_states: Optional[torch.Tensor], scale: float, sp=None):
+def joint_attention_core(attn, proc, x: torch.Tensor, text_len: int, rope, ip_hidden_states: Optional[torch.Tensor], scale: float, sp=None,
+                         fp8_qkv: bool = False):
     """attn_processor.py:209-273 on the joint [text ; video] sequence x [B, S, D] (bf16, contiguous).
     Returns the attention output BEFORE to_out: `o + scale * ip_attention(to_q_ip(o))`.
     `sp` (dist.SequenceParallel): x holds only this rank's rows (text_len / rope already local); K and V rows of all ranks are
-    all-gathered after qk-norm + RoPE, everything else stays local."""
+    all-gathered after qk-norm + RoPE, everything else stays local.
+    `fp8_qkv` (cogvideox.set_linear_precision): the fused QKV projection on the e4m3 GEMM, then the stand-alone qk-norm + RoPE kernel; ignored
+    under `sp` (the sharded projection's [K | V]-first order lives in the bf16 GEMM's fused epilogue)."""
     B, S, D = x.shape
     H = attn.heads
     fw = proc._fused
@@ -126,6 +129,16 @@ def joint_attention_core(attn, proc, x: torch.Tensor, text_len: int, rope, ip_hi
     nq, nk = getattr(attn, "norm_q", None), getattr(attn, "norm_k", None)
     if sp is not None:
         o = _sharded_attention(attn, x, wqkv, bqkv, H, nq, nk, cos, sin, text_len, sp)
+        return _motion_branch(attn, proc, o, ip_hidden_states, scale)
+    if fp8_qkv:
+        # the concatenated weight quantised once per output channel; the projection with a plain epilogue, then norm_q / norm_k + RoPE in place
+        # (the two-kernel form ops.qkv_linear_qknorm_rope falls back to)
+        w8, w_exp = fw.get(("qkv8", _wkey(attn.to_q.weight), _wkey(attn.to_k.weight), _wkey(attn.to_v.weight)), lambda: ops.quant_rows_e4m3(wqkv))
+        qkv = ops.linear_fp8(x, w8, w_exp, bqkv)
+        ops.qknorm_rope_(qkv, H, nq.weight if nq is not None else None, nq.bias if nq is not None else None, nk.weight if nk is not None else None,
+                         nk.bias if nk is not None else None, cos, sin, text_len, eps=nq.eps if nq is not None else 1e-6, q_premul=ops.LOG2E * 64 ** -0.5)
+        q5 = qkv.view(B, S, 3, H, 64)
+        o = ops.attention(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], q_prescaled=True)
         return _motion_branch(attn, proc, o, ip_hidden_states, scale)
     # :209-211 + :220-231 in ONE GEMM: the projection's epilogue applies norm_q / norm_k and the rotary embedding to the Q and K thirds
     qkv = ops.qkv_linear_qknorm_rope(x, wqkv, bqkv, H, nq.weight if nq is not None else None, nq.bias if nq is not None else None,

@@ -28,7 +28,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .attn_processor import APAdapterCogVideoXAttnProcessor2_0, Attention, joint_attention_core
+from .attn_processor import APAdapterCogVideoXAttnProcessor2_0, Attention, _wkey, joint_attention_core
 
 
 class _LayerNormZero(nn.Module):
@@ -94,8 +94,29 @@ class _PlainProcessor:
         self.scale = [0.0]
 
 
+LINEAR_SITES = ("qkv", "to_out", "ff1", "ff2")   # the four large linears of a CogVideoXBlock (set_linear_precision)
+
+
+def set_linear_precision(model: "CogVideoXTransformer3DModel", precision: str = "bf16", sites=LINEAR_SITES) -> "CogVideoXTransformer3DModel":
+    """'bf16' (the reference's precision: every call exactly where it is without this option) or 'fp8': the named sites of every CogVideoXBlock --
+    "qkv" (to_q / to_k / to_v, attn_processor.py:209-211), "to_out" (:276), "ff1" / "ff2" (diffusers FeedForward) -- run on the e4m3 GEMM
+    (ops.linear_fp8): activations quantised per row in front of each GEMM, weights per output channel, lazily and once.  Under sequence sharding
+    the QKV projection stays bf16.  The motion branch, the embeddings, the modulation GEMM and proj_out are bf16 either way."""
+    if precision not in ("bf16", "fp8"):
+        raise ValueError("precision must be 'bf16' or 'fp8'")
+    sites = tuple(sites)
+    bad = [s for s in sites if s not in LINEAR_SITES]
+    if bad:
+        raise ValueError(f"unknown linear site(s) {bad}: choose from {LINEAR_SITES}")
+    model.linear_precision = precision
+    model.linear_fp8_sites = frozenset(sites) if precision == "fp8" else frozenset()
+    return model
+
+
 class CogVideoXTransformer3DModel(nn.Module):
     """CogVideoX-5B-I2V DiT (rotary + learned positional embedding flavour)."""
+    linear_precision = "bf16"          # set_linear_precision
+    linear_fp8_sites = frozenset()
 
     def __init__(self, num_layers=42, num_attention_heads=48, attention_head_dim=64, in_channels=32, out_channels=16, time_embed_dim=512,
                  text_embed_dim=4096, max_text_seq_length=226, patch_size=2, sample_frames=13, sample_height=60, sample_width=90,
@@ -119,6 +140,8 @@ class CogVideoXTransformer3DModel(nn.Module):
         self.proj_out = nn.Linear(D, patch_size * patch_size * out_channels)
         self._fused: Dict[str, torch.Tensor] = {}
         self._plain = _PlainProcessor()
+        from .attn_processor import _FusedWeights
+        self._fp8_weights = _FusedWeights()                        # (site, layer) -> the weight's e4m3 rows + exponents (set_linear_precision)
 
     # ---- diffusers-style processor plumbing (cogvideox/module.py:163-175 uses exactly these two) ----
     @property
@@ -223,21 +246,30 @@ class CogVideoXTransformer3DModel(nn.Module):
             off = (layer_slot * 6 + j) * D
             return mod[:, off:off + D]
 
+        fp8 = self.linear_fp8_sites
+
+        def site_linear(site: str, layer: int, inp: torch.Tensor, lin: nn.Linear, **kw) -> torch.Tensor:
+            """one of the block's large linears in the precision its site is set to"""
+            if site not in fp8:
+                return ops.linear(inp, lin.weight, lin.bias, **kw)
+            w8, w_exp = self._fp8_weights.get(((site, layer), _wkey(lin.weight)), lambda: ops.quant_rows_e4m3(lin.weight.detach()))
+            return ops.linear_fp8(inp, w8, w_exp, lin.bias, **kw)
+
         for i, blk in enumerate(self.transformer_blocks):
             proc = blk.attn1.processor if isinstance(blk.attn1.processor, APAdapterCogVideoXAttnProcessor2_0) else self._plain
             # norm1: shift, scale, gate, enc_shift, enc_scale, enc_gate = chunk(6)
             nh = ops.layernorm(x, blk.norm1.norm.weight, blk.norm1.norm.bias, cfg["norm_eps"], shift0=chunk(2 * i, 3), scale0=chunk(2 * i, 4),
                                shift1=chunk(2 * i, 0), scale1=chunk(2 * i, 1), rows_per_batch=S, split=Lt, mod_stride=ms)
             scale = proc.scale[0] if ip is not None else 0.0
-            o = joint_attention_core(blk.attn1, proc, nh, Lt, rope, ip, scale, sp=sp)
-            ops.linear(o, blk.attn1.to_out[0].weight, blk.attn1.to_out[0].bias, out=x, epilogue=ops.EPI_GATE_RESID, resid=x,
-                       gate0=chunk(2 * i, 5), gate1=chunk(2 * i, 2), rows_per_batch=S, split=Lt, gate_stride=ms)
+            o = joint_attention_core(blk.attn1, proc, nh, Lt, rope, ip, scale, sp=sp, fp8_qkv="qkv" in fp8)
+            site_linear("to_out", i, o, blk.attn1.to_out[0], out=x, epilogue=ops.EPI_GATE_RESID, resid=x,
+                        gate0=chunk(2 * i, 5), gate1=chunk(2 * i, 2), rows_per_batch=S, split=Lt, gate_stride=ms)
             nh = ops.layernorm(x, blk.norm2.norm.weight, blk.norm2.norm.bias, cfg["norm_eps"], shift0=chunk(2 * i + 1, 3),
                                scale0=chunk(2 * i + 1, 4), shift1=chunk(2 * i + 1, 0), scale1=chunk(2 * i + 1, 1), rows_per_batch=S,
                                split=Lt, mod_stride=ms, out=nh)
-            f = ops.linear(nh, blk.ff.net[0].proj.weight, blk.ff.net[0].proj.bias, epilogue=ops.EPI_GELU_TANH)
-            ops.linear(f, blk.ff.net[2].weight, blk.ff.net[2].bias, out=x, epilogue=ops.EPI_GATE_RESID, resid=x,
-                       gate0=chunk(2 * i + 1, 5), gate1=chunk(2 * i + 1, 2), rows_per_batch=S, split=Lt, gate_stride=ms)
+            f = site_linear("ff1", i, nh, blk.ff.net[0].proj, epilogue=ops.EPI_GELU_TANH)
+            site_linear("ff2", i, f, blk.ff.net[2], out=x, epilogue=ops.EPI_GATE_RESID, resid=x,
+                        gate0=chunk(2 * i + 1, 5), gate1=chunk(2 * i + 1, 2), rows_per_batch=S, split=Lt, gate_stride=ms)
 
         # tail: norm_final over the joint sequence, AdaLayerNorm (shift, scale = chunk(2)), proj_out, unpatchify
         y = ops.layernorm(x, self.norm_final.weight, self.norm_final.bias, cfg["norm_eps"])

@@ -12,7 +12,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, GemmArgs, LnArgs, QkNormRopeArgs, check
+from ._lib import AttnArgs, GemmArgs, GemmFp8Args, LnArgs, QkNormRopeArgs, check
 
 EPI_NONE, EPI_GELU_TANH, EPI_GELU_ERF, EPI_RESID, EPI_GATE_RESID, EPI_SILU, EPI_GEGLU, EPI_QKNORM_ROPE = range(8)
 LOG2E = 1.4426950408889634
@@ -431,6 +431,78 @@ def qkv_linear_qknorm_rope(x: torch.Tensor, weight: torch.Tensor, bias: Optional
         linear(x, weight, bias, out=out)
         return qknorm_rope_(out, H, q_gamma, q_beta, k_gamma, k_beta, cos, sin, text_len, eps=eps, q_premul=q_premul)
     check(rc, "mrag_gemm_bf16")
+    return out
+
+
+def fp8_launch_counts() -> dict:
+    """launches of the fp8 linear path's two entry points so far (host-side counters beside the dispatch table): {"gemm": n, "quant": n}"""
+    buf = (ctypes.c_uint64 * 2)()
+    _lib.lib().mrag_fp8_launch_counts(buf, 2)
+    return {"gemm": int(buf[0]), "quant": int(buf[1])}
+
+
+def fp8_linear_supported(N: int, K: int) -> bool:
+    """shapes mrag_gemm_fp8 takes (include/mrag_hip.h): whole 128-deep K-tiles, 16-byte aligned output rows; any row count"""
+    return N > 0 and K > 0 and K % 128 == 0 and N % 16 == 0
+
+
+def quant_rows_e4m3(x: torch.Tensor, out: Optional[tuple] = None):
+    """per-row power-of-two scaled e4m3 copy of x [..., K] bf16 (mrag_quant_rows_e4m3): returns (x8, exp) with x8 [M, K] uint8 holding OCP e4m3fn
+    bytes (`x8.view(torch.float8_e4m3fn)`) and exp [M] int32, x8 = rne(x * 2^exp), exp the largest power that keeps the row inside +-448.
+    `out` = (x8, exp) buffers to fill (x8 rows 16-byte aligned).  The same call quantises nn.Linear weights [N, K] per output channel."""
+    _dev(x, name="x")
+    x2 = _rows(x)
+    M, K = x2.shape
+    if K % 16 != 0 or x2.stride(0) % 8 != 0 or x2.data_ptr() % 16 != 0:
+        raise ValueError(f"quant_rows_e4m3: K % 16 == 0 and 16-byte aligned rows (got K={K}, row stride {x2.stride(0)})")
+    if out is None:
+        out = (torch.empty(M, K, dtype=torch.uint8, device=x.device), torch.empty(M, dtype=torch.int32, device=x.device))
+    x8, ex = out
+    _dev(x8, torch.uint8, "x8"); _dev(ex, torch.int32, "exp")
+    if tuple(x8.shape) != (M, K) or x8.stride(1) != 1 or tuple(ex.shape) != (M,) or not ex.is_contiguous():
+        raise ValueError("quant_rows_e4m3: out = (x8 [M, K] uint8 with contiguous rows, exp [M] int32)")
+    check(_lib.lib().mrag_quant_rows_e4m3(_stream(), _p(x2), _p(x8), _p(ex), M, K, x2.stride(0), x8.stride(0)), "mrag_quant_rows_e4m3")
+    return x8, ex
+
+
+def linear_fp8(x: torch.Tensor, w8: torch.Tensor, w_exp: torch.Tensor, bias: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None,
+               epilogue: int = EPI_NONE, resid: Optional[torch.Tensor] = None, gate0: Optional[torch.Tensor] = None,
+               gate1: Optional[torch.Tensor] = None, rows_per_batch: int = 0, split: int = 0, gate_stride: int = 0) -> torch.Tensor:
+    """out = epilogue(x @ W.T + bias) on the e4m3 MFMA path: x [..., K] bf16 is quantised per row into a grow-only workspace of the (device, stream),
+    (w8, w_exp) = quant_rows_e4m3(weight) is the weight quantised once per output channel.  Epilogues EPI_NONE / EPI_GELU_TANH / EPI_RESID /
+    EPI_GATE_RESID as in `linear` (out may be resid).  Two launches, nothing read back: capturable into a HIP graph.  Raises on shapes the kernel
+    does not take (`fp8_linear_supported`): opting in is explicit, so is its refusal."""
+    _dev(x, name="x"); _dev(w8, torch.uint8, "w8"); _dev(w_exp, torch.int32, "w_exp")
+    if bias is not None:
+        _dev(bias, name="bias")
+    x2 = _rows(x)
+    M, K = x2.shape
+    N = w8.shape[0]
+    if w8.dim() != 2 or w8.shape[1] != K or w8.stride(1) != 1 or tuple(w_exp.shape) != (N,) or not w_exp.is_contiguous():
+        raise ValueError(f"linear_fp8: w8 {tuple(w8.shape)} / w_exp {tuple(w_exp.shape)} do not match K={K}")
+    if not fp8_linear_supported(N, K):
+        raise ValueError(f"linear_fp8: N={N}, K={K} outside the fp8 GEMM's shapes (K % 128 == 0, N % 16 == 0)")
+    if epilogue not in (EPI_NONE, EPI_GELU_TANH, EPI_RESID, EPI_GATE_RESID):
+        raise ValueError(f"linear_fp8: epilogue {epilogue} does not exist on the fp8 GEMM")
+    exp_bytes = (M * 4 + 255) // 256 * 256
+    ws = _attn_workspace(x.device, exp_bytes + M * K, "fp8lin")
+    a_exp, a8 = ws[:M * 4].view(torch.int32), ws[exp_bytes:exp_bytes + M * K].view(M, K)
+    quant_rows_e4m3(x2, out=(a8, a_exp))
+    if out is None:
+        out = torch.empty(*x.shape[:-1], N, dtype=torch.bfloat16, device=x.device)
+    o2 = _rows(_dev(out, name="out"))
+    a = GemmFp8Args()
+    a.A8, a.W8, a.a_exp, a.w_exp, a.bias, a.C = _p(a8), _p(w8), _p(a_exp), _p(w_exp), _p(bias), _p(o2)
+    a.M, a.N, a.K = M, N, K
+    a.lda, a.ldw, a.ldc = a8.stride(0), w8.stride(0), o2.stride(0)
+    a.epilogue = epilogue
+    if resid is not None:
+        r2 = _rows(_dev(resid, name="resid"))
+        a.resid, a.ldr = _p(r2), r2.stride(0)
+    if epilogue == EPI_GATE_RESID:
+        a.gate0, a.gate1 = _p(_dev(gate0, name="gate0")), _p(_dev(gate1, name="gate1"))
+        a.rows_per_batch, a.split, a.gate_stride = rows_per_batch, split, gate_stride
+    check(_lib.lib().mrag_gemm_fp8(_stream(), ctypes.byref(a)), "mrag_gemm_fp8")
     return out
 
 
