@@ -487,11 +487,8 @@ static int launch16_plain(hipStream_t s, AttnP p) {
   constexpr int ROWS = NW * QB * 16;
   const size_t lds = 2 * NS * TILE_BYTES;
   p.n_qtiles = (p.Sq + ROWS - 1) / ROWS;
-  const void* kf = (const void*)attn16_kernel<QB, NW, NS, false>;
-  const hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  MRAG_LAUNCH((attn16_kernel<QB, NW, NS, false>), dim3(p.n_qtiles * p.B * p.H), dim3(NW * 64), lds, s, p);
-  MRAG_LAUNCH_CHECK();
+  const int rc = launch_dyn_lds(attn16_kernel<QB, NW, NS, false>, dim3(p.n_qtiles * p.B * p.H), dim3(NW * 64), lds, s, p);
+  if (rc != MRAG_OK) return rc;
   MRAG_COUNT(MRAG_K_ATTN16);
   return MRAG_OK;
 }
@@ -505,11 +502,8 @@ static int launch16_split(hipStream_t s, AttnP p, const SplitPlan* pl, void* wor
   p.kv_splits = pl->splits; p.chunk_keys = pl->chunk_keys; p.rem_rows = pl->rem_rows; p.tile_rows = NW * QB * 16;
   p.part_o = (float*)workspace;
   p.part_ml = (float2*)((char*)workspace + (size_t)nbh * pl->splits * pl->rem_rows * 64 * sizeof(float));
-  const void* kf = (const void*)attn16_kernel<QB, NW, NS, true>;
-  const hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  MRAG_LAUNCH((attn16_kernel<QB, NW, NS, true>), dim3(p.n_main + nbh * pl->splits), dim3(NW * 64), lds, s, p);
-  MRAG_LAUNCH_CHECK();
+  const int rc = launch_dyn_lds(attn16_kernel<QB, NW, NS, true>, dim3(p.n_main + nbh * pl->splits), dim3(NW * 64), lds, s, p);
+  if (rc != MRAG_OK) return rc;
   MRAG_COUNT(MRAG_K_ATTN16_KSPLIT);
   return mrag_launch_attn_combine(s, p);
 }

@@ -36,7 +36,7 @@ namespace {
 constexpr float kThr = 5.0f;          // deferred-rescale threshold in log2 units (P <= 32)
 constexpr int KVB = 64;               // keys per tile
 constexpr int TILE_BYTES = KVB * 128; // one K (or V) tile
-constexpr int NS = 4;   // LDS ring stages per operand (DMA runs D = NS-2 tiles ahead); 2 x 64 KB fit two workgroups per CU
+constexpr int NS = 4;   // LDS ring stages per operand (DMA runs D = NS-1 tiles ahead); 2 x 64 KB fit two workgroups per CU
 constexpr int V_BASE = NS * TILE_BYTES;  // LDS: K stages 0..NS-1, then V stages 0..NS-1
 
 __device__ __forceinline__ bf16x8 scale_frag(u32x4 raw, float s) {
@@ -57,7 +57,7 @@ __device__ __forceinline__ float half_swap_max(float v) {
 
 struct Lane {
   int hh, k_row_off, k_swz, v_lane_off, v_half0, v_half1, head;
-  unsigned kb[4], vc0, vc1;   // loop-invariant LDS addresses of this lane's K fragment chunks / V^T reads in ring stage 0 (MRAG_ATTN_IMM_STAGE)
+  unsigned kb[4], vc0, vc1;   // loop-invariant LDS addresses of this lane's K fragment chunks / V^T reads in ring stage 0 (the stage itself is an instruction immediate: qk_tile_imm8 / pv_tile_imm)
 };
 
 struct NoHook {
@@ -103,7 +103,7 @@ __device__ __forceinline__ void qk_tile(const char* kst, const Lane& ln, const b
 // O^T += V^T . P^T (8 MFMAs).  The 16 transposed reads go through ONE asm statement: hipcc cannot see that the
 // ds_read_tr16 builtin does not alias the in-flight LDS-DMA of later tiles and would drain it (s_waitcnt vmcnt(0))
 // in the middle of the tile.  EXEC is all ones here (wave-uniform control flow only).
-__device__ __forceinline__ void pv_tile(const char* vst, const Lane& ln, const bf16x8 (&pb)[4], f32x16& o0, f32x16& o1, f32x16& lacc) {
+__device__ __forceinline__ void pv_tile(const char* vst, const Lane& ln, const bf16x8 (&pb)[4], f32x16& o0, f32x16& o1) {
   {
     const unsigned c0 = (unsigned)(size_t)(vst + ln.v_lane_off + ln.v_half0), c1 = (unsigned)(size_t)(vst + ln.v_lane_off + ln.v_half1);
 #pragma unroll
@@ -131,29 +131,6 @@ __device__ __forceinline__ void pv_tile(const char* vst, const Lane& ln, const b
 // The ring stage as an INSTRUCTION IMMEDIATE (ds_read offset field) instead of per-tile address arithmetic: the main loop is unrolled by
 // NS, so `t % NS` is a compile-time constant, the lane's base addresses are loop-invariant registers, and ~11 integer vector instructions
 // per tile (of ~144) disappear from a loop whose vector pipe is ~77 % busy.
-template <int STG, typename Between = NoHook>
-__device__ __forceinline__ void qk_tile_imm(const Lane& ln, const bf16x8 (&qf)[4], const f32x16& negm, f32x16& s0, f32x16& s1, Between between = Between()) {
-  u32x4 kf[4];
-  asm volatile("ds_read_b128 %0, %4 offset:%8\n\tds_read_b128 %1, %5 offset:%8\n\tds_read_b128 %2, %6 offset:%8\n\tds_read_b128 %3, %7 offset:%8"
-               : "=&v"(kf[0]), "=&v"(kf[1]), "=&v"(kf[2]), "=&v"(kf[3]) : "v"(ln.kb[0]), "v"(ln.kb[1]), "v"(ln.kb[2]), "v"(ln.kb[3]), "n"(STG * TILE_BYTES) : "memory");
-  between();
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kf[0]), "+v"(kf[1]), "+v"(kf[2]), "+v"(kf[3]) :: "memory");
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  const u32x4 kneg = {ln.hh == 0 ? 0x0000bf80u : 0u, 0u, 0u, 0u};
-  const u32x4 qm = {__float_as_uint(negm[1]), 0u, 0u, 0u};
-  s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[0]), qf[0], zero, 0, 0, 0);
-#pragma unroll
-  for (int ks = 1; ks < 4; ++ks) s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[ks]), qf[ks], s0, 0, 0, 0);
-  asm volatile("ds_read_b128 %0, %4 offset:%8\n\tds_read_b128 %1, %5 offset:%8\n\tds_read_b128 %2, %6 offset:%8\n\tds_read_b128 %3, %7 offset:%8\n\t"
-               "s_waitcnt lgkmcnt(0)"
-               : "=&v"(kf[0]), "=&v"(kf[1]), "=&v"(kf[2]), "=&v"(kf[3]) : "v"(ln.kb[0]), "v"(ln.kb[1]), "v"(ln.kb[2]), "v"(ln.kb[3]), "n"(STG * TILE_BYTES + 4096) : "memory");
-  s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[0]), qf[0], zero, 0, 0, 0);
-#pragma unroll
-  for (int ks = 1; ks < 4; ++ks) s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf[ks]), qf[ks], s1, 0, 0, 0);
-  s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kneg), __builtin_bit_cast(bf16x8, qm), s0, 0, 0, 0);
-  s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kneg), __builtin_bit_cast(bf16x8, qm), s1, 0, 0, 0);
-}
-
 template <int STG>
 __device__ __forceinline__ void pv_tile_imm(const Lane& ln, const bf16x8 (&pb)[4], f32x16& o0, f32x16& o1) {
 #pragma unroll
@@ -186,7 +163,7 @@ __device__ __forceinline__ void pv_tile_imm(const Lane& ln, const bf16x8 (&pb)[4
   }
 }
 
-// Both 32-key blocks' fragments requested UP FRONT (8 K reads / 16 V^T reads in flight, released to the MFMAs by counted lgkmcnt waits --
+// Both 32-key blocks' K fragments requested UP FRONT (8 reads in flight, released to the MFMAs by counted lgkmcnt waits --
 // LDS reads return in order): the second block's LDS latency hides under the first block's MFMAs instead of being paid behind them.  The LDS
 // pipe is only ~25 % busy in this loop (256 B/clk per CU, tools/exp/lds_rate.hip; SQ_LDS_IDX_ACTIVE), so what the reads cost is their latency.
 template <int STG, typename Between = NoHook>
@@ -212,49 +189,17 @@ __device__ __forceinline__ void qk_tile_imm8(const Lane& ln, const bf16x8 (&qf)[
   s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kneg), __builtin_bit_cast(bf16x8, qm), s1, 0, 0, 0);
 }
 
-template <int STG>
-__device__ __forceinline__ void pv_tile_imm16(const Lane& ln, const bf16x8 (&pb)[4], f32x16& o0, f32x16& o1) {
-  u32x2 u0[8], u1[8];
-  asm volatile("ds_read_b64_tr_b16 %0, %8 offset:%10\n\tds_read_b64_tr_b16 %1, %8 offset:%11\n\t"
-               "ds_read_b64_tr_b16 %4, %9 offset:%10\n\tds_read_b64_tr_b16 %5, %9 offset:%11\n\t"
-               "ds_read_b64_tr_b16 %2, %8 offset:%12\n\tds_read_b64_tr_b16 %3, %8 offset:%13\n\t"
-               "ds_read_b64_tr_b16 %6, %9 offset:%12\n\tds_read_b64_tr_b16 %7, %9 offset:%13"
-               : "=&v"(u0[0]), "=&v"(u0[1]), "=&v"(u0[2]), "=&v"(u0[3]), "=&v"(u1[0]), "=&v"(u1[1]), "=&v"(u1[2]), "=&v"(u1[3])
-               : "v"(ln.vc0), "v"(ln.vc1), "n"(STG * TILE_BYTES), "n"(STG * TILE_BYTES + 1024), "n"(STG * TILE_BYTES + 2048), "n"(STG * TILE_BYTES + 3072) : "memory");
-  asm volatile("ds_read_b64_tr_b16 %0, %8 offset:%10\n\tds_read_b64_tr_b16 %1, %8 offset:%11\n\t"
-               "ds_read_b64_tr_b16 %4, %9 offset:%10\n\tds_read_b64_tr_b16 %5, %9 offset:%11\n\t"
-               "ds_read_b64_tr_b16 %2, %8 offset:%12\n\tds_read_b64_tr_b16 %3, %8 offset:%13\n\t"
-               "ds_read_b64_tr_b16 %6, %9 offset:%12\n\tds_read_b64_tr_b16 %7, %9 offset:%13\n\t"
-               "s_waitcnt lgkmcnt(8)"
-               : "=&v"(u0[4]), "=&v"(u0[5]), "=&v"(u0[6]), "=&v"(u0[7]), "=&v"(u1[4]), "=&v"(u1[5]), "=&v"(u1[6]), "=&v"(u1[7])
-               : "v"(ln.vc0), "v"(ln.vc1), "n"(STG * TILE_BYTES + 4096), "n"(STG * TILE_BYTES + 5120), "n"(STG * TILE_BYTES + 6144), "n"(STG * TILE_BYTES + 7168) : "memory");
-  asm volatile("" : "+v"(u0[0]), "+v"(u0[1]), "+v"(u0[2]), "+v"(u0[3]), "+v"(u1[0]), "+v"(u1[1]), "+v"(u1[2]), "+v"(u1[3]));   // half 0 has landed
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    if (half == 1)
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(u0[4]), "+v"(u0[5]), "+v"(u0[6]), "+v"(u0[7]), "+v"(u1[4]), "+v"(u1[5]), "+v"(u1[6]), "+v"(u1[7]) :: "memory");
-#pragma unroll
-    for (int k2 = 0; k2 < 2; ++k2) {
-      const int i = half * 4 + 2 * k2;
-      const u32x4 w0 = {u0[i][0], u0[i][1], u0[i + 1][0], u0[i + 1][1]};
-      const u32x4 w1 = {u1[i][0], u1[i][1], u1[i + 1][0], u1[i + 1][1]};
-      o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w0), pb[2 * half + k2], o0, 0, 0, 0);
-      o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w1), pb[2 * half + k2], o1, 0, 0, 0);
-    }
-  }
-}
-
 struct Run {
   f32x16 o0, o1, negm;
-  f32x16 lacc;   // row sums, accumulated by the matrix pipe: lacc = ones . P^T (every register of a lane holds l of its query)
+  f32x16 lacc;   // row sum: element 0 holds the lane's half of l of its query, accumulated by v_dot2c over the bf16 P pairs (softmax_tile)
   float m;
 };
 
 // softmax bookkeeping of one tile: masks, tile max, deferred rescale, P = exp2(S'), row sum, bf16 B fragments.
 // register i of block kb holds key t*64 + kb*32 + (i&3) + 8*(i>>2) + 4*hh for query (lane & 31).
-template <bool HAS_MASK, bool HAS_NEXT, typename Mid = NoHook>
+template <bool HAS_MASK>
 __device__ __forceinline__ void softmax_tile(const AttnP& p, const int skv, const Lane& ln, int t, int nt, int qrow_c, f32x16& s0, f32x16& s1,
-                                             f32x16& n0, f32x16& n1, Run& r, bf16x8 (&pb)[4], Mid mid = Mid()) {
+                                             Run& r, bf16x8 (&pb)[4]) {
   // skv = keys this workgroup scans (p.Skv, or its chunk of them in the key-split tail; the mask path is never split)
   // key held by register i of block kb: tile_start + kb*32 + (i&3) + 8*(i>>2) + 4*hh; the last tile of a long sequence starts at
   // Skv-64 (slid back), keys before t*64 were already consumed by the previous tile
@@ -326,12 +271,7 @@ __device__ __forceinline__ void softmax_tile(const AttnP& p, const int skv, cons
     r.negm[1] = __uint_as_float(ln.hh == 0 ? (unsigned)f2bf(r.m) : 0u);   // query-side fragment (m, 0, ..., 0) of the max-subtracting k-step
 #pragma unroll
     for (int i = 0; i < 16; ++i) { s0[i] -= delta; s1[i] -= delta; }
-    if constexpr (HAS_NEXT) {  // the prefetched S' of tile t+1 was formed against the old max
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { n0[i] -= delta; n1[i] -= delta; }
-    }
   }
-  mid();  // staggered waves rendezvous here (between the max / rescale head and the exp body)
   float la = 0.f, lb = 0.f;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
@@ -498,56 +438,41 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && !HAS_MASK) ? 4 : 1) void attn_
     asm volatile("" ::: "memory");
   };
   {
-    // iteration t reads K(t), V(t) from stage t % NS.  Barrier #j guarantees tile j has landed for every wave; after it each
-    // wave issues tile j + D into the stage of tile j - 2 (ring of NS = D + 2).  The "late" half of the workgroup (waves
-    // NW/2..NW-1, the SIMD partners of the early half) runs HALF A TILE BEHIND: it takes barrier #j in the middle of its
-    // softmax(j-1), so while one wave of a SIMD is in its MFMA phase (QK^T / PV) its partner is in its exp/convert phase,
-    // instead of both queueing on the same pipe right after a common barrier.
-    const bool late = false;
+    // iteration t reads K(t), V(t) from stage t % NS.  Barrier #t guarantees tile t has landed for every wave; after it each
+    // wave issues tile t + D into the stage of tile t - 1, which every wave has finished reading (ring of NS = D + 1).  All waves of
+    // the workgroup run in step.
 #pragma unroll
     for (int i = 0; i < D; ++i) { issue_k(i, i); issue_v(i, i); }
-    if (late) { wait_pair(); issue_k(D % NS, D); issue_v(D % NS, D); }   // barrier #0
-    auto iter = [&](int t, auto split_c, auto stage_c) {
+    auto iter = [&](int t, auto stage_c) {
       constexpr int STG = decltype(stage_c)::value;   // ring stage as a compile-time constant, or -1
-      if (!late) wait_pair();   // barrier #t
-      auto early_issue = [&]() {
-        if (!late) { issue_k((t + D) % NS, t + D); issue_v((t + D) % NS, t + D); }
-      };
-      auto mid = [&]() {
-        if (late) { wait_pair(); issue_k((t + 1 + D) % NS, t + 1 + D); issue_v((t + 1 + D) % NS, t + 1 + D); }   // barrier #(t+1)
-      };
-      if (!wave_active) { early_issue(); mid(); return; }
+      wait_pair();   // barrier #t
+      auto early_issue = [&]() { issue_k((t + D) % NS, t + D); issue_v((t + D) % NS, t + D); };
+      if (!wave_active) { early_issue(); return; }
       f32x16 s0, s1;
       bf16x8 pb[4];
       if constexpr (STG >= 0) qk_tile_imm8<STG>(ln, qf, r.negm, s0, s1, early_issue);
-      else
-      qk_tile(smem + (t % NS) * TILE_BYTES, ln, qf, r.negm, s0, s1, early_issue);
-      softmax_tile<HAS_MASK, false>(p, skv, ln, t, nt, qrow_c, s0, s1, s0, s1, r, pb, mid);
+      else qk_tile(smem + (t % NS) * TILE_BYTES, ln, qf, r.negm, s0, s1, early_issue);
+      softmax_tile<HAS_MASK>(p, skv, ln, t, nt, qrow_c, s0, s1, r, pb);
       if constexpr (STG >= 0) pv_tile_imm<STG>(ln, pb, r.o0, r.o1);
-      else
-      pv_tile(smem + V_BASE + (t % NS) * TILE_BYTES, ln, pb, r.o0, r.o1, r.lacc);
-        };
-    // full unmasked tiles take the per-block pipeline; the ragged last tile (and the masked instantiation) the one-softmax path,
-    // in separate loops so that neither path's live state burdens the other
-    const int n_split = 0;
+      else pv_tile(smem + V_BASE + (t % NS) * TILE_BYTES, ln, pb, r.o0, r.o1);
+    };
     using RT = std::integral_constant<int, -1>;
-    for (int t = 0; t < n_split; ++t) iter(t, std::true_type{}, RT{});
-    int t = n_split;
+    int t = 0;
     if constexpr (NS == 4 && NW == 8 && !HAS_MASK && !SHORTKV) {
-      // unrolled by the ring depth: stage = t % NS is an immediate (n_split is 0 here, so t starts at a multiple of NS)
+      // unrolled by the ring depth: stage = t % NS is an immediate (t starts at 0 and advances by NS)
       for (; t + NS <= nt; t += NS) {
-        iter(t, std::false_type{}, std::integral_constant<int, 0>{});
-        iter(t + 1, std::false_type{}, std::integral_constant<int, 1>{});
-        iter(t + 2, std::false_type{}, std::integral_constant<int, 2>{});
-        iter(t + 3, std::false_type{}, std::integral_constant<int, 3>{});
+        iter(t, std::integral_constant<int, 0>{});
+        iter(t + 1, std::integral_constant<int, 1>{});
+        iter(t + 2, std::integral_constant<int, 2>{});
+        iter(t + 3, std::integral_constant<int, 3>{});
       }
     }
-    for (; t < nt; ++t) iter(t, std::false_type{}, RT{});
+    for (; t < nt; ++t) iter(t, RT{});   // the tiles left over, and every other instantiation: the stage from t % NS
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // retire the clamped tail DMAs before the LDS is released
 
   if (!wave_active) return;
-  // ---- epilogue: normalise by the MFMA-accumulated row sum (already complete over both half-waves' keys), fused residual
+  // ---- epilogue: the two half-waves' row sums (each over its own keys) are added, then normalise; fused residual
   if (qrow >= p.Sq) return;
   {
     const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(r.lacc[0]), __float_as_uint(r.lacc[0]), false, false);
@@ -597,14 +522,8 @@ int launch_attn(hipStream_t s, AttnP p) {
   p.n_qtiles = (p.Sq + NW * 32 - 1) / (NW * 32);
   const dim3 grid(p.n_qtiles * p.B * p.H), block(NW * 64);
   const size_t lds = 2 * NS * TILE_BYTES;
-  {
-    const void* kf = (p.mask || p.bias) ? (const void*)attn_fwd_kernel<NW, true, SHORTKV> : (const void*)attn_fwd_kernel<NW, false, SHORTKV>;
-    const hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  if (p.mask || p.bias) MRAG_LAUNCH((attn_fwd_kernel<NW, true, SHORTKV>), grid, block, lds, s, p);
-  else MRAG_LAUNCH((attn_fwd_kernel<NW, false, SHORTKV>), grid, block, lds, s, p);
-  MRAG_LAUNCH_CHECK();
+  const int rc = launch_dyn_lds((p.mask || p.bias) ? attn_fwd_kernel<NW, true, SHORTKV> : attn_fwd_kernel<NW, false, SHORTKV>, grid, block, lds, s, p);
+  if (rc != MRAG_OK) return rc;
   MRAG_COUNT(MRAG_K_ATTN_FLASH);
   return MRAG_OK;
 }
@@ -676,11 +595,8 @@ int launch_attn_split(hipStream_t s, AttnP p, const SplitPlan& pl, void* workspa
   p.part_o = (float*)workspace;
   p.part_ml = (float2*)((char*)workspace + (size_t)nbh * pl.splits * pl.rem_rows * 64 * sizeof(float));
   const size_t lds = 2 * NS * TILE_BYTES;
-  const void* kf = (const void*)attn_fwd_kernel<8, false, false, true>;
-  const hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  MRAG_LAUNCH((attn_fwd_kernel<8, false, false, true>), dim3(p.n_main + nbh * pl.splits), dim3(512), lds, s, p);
-  MRAG_LAUNCH_CHECK();
+  const int rc = launch_dyn_lds(attn_fwd_kernel<8, false, false, true>, dim3(p.n_main + nbh * pl.splits), dim3(512), lds, s, p);
+  if (rc != MRAG_OK) return rc;
   MRAG_COUNT(MRAG_K_ATTN_FLASH_KSPLIT);
   MRAG_LAUNCH(attn_combine_kernel, dim3((unsigned)(((long long)nbh * pl.rem_rows + 15) / 16)), dim3(256), 0, s, p);
   MRAG_LAUNCH_CHECK();
@@ -898,8 +814,6 @@ extern "C" int mrag_ip_attn_folded_bf16(void* stream, const void* scores, const 
   constexpr int HG = IPFOLD_HG;
   const size_t lds = HG * 64 * 32 * sizeof(bf16_t);
   const long long groups = ((long long)kv_batch_div * S + 63) / 64;
-  hipError_t e = hipFuncSetAttribute((const void*)ip_attn_folded_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
   // ONE round of resident workgroups (each pays a V^T fill and then walks its share of the rows): the count the RUNTIME reports for this kernel's registers
   // and LDS.  Until round 6 the grid assumed eight workgroups per CU from the LDS size alone; the kernel's 72 VGPRs allow seven -- 2 040 workgroups on 1 792
   // slots, i.e. a second round for an eighth of them.
@@ -911,8 +825,8 @@ extern "C" int mrag_ip_attn_folded_bf16(void* stream, const void* scores, const 
   }
   const long long per = (256LL * wg_per_cu) / (((H + HG - 1) / HG) * (long long)(B / kv_batch_div));
   const unsigned gx = (unsigned)(groups < (per > 1 ? per : 1) ? groups : (per > 1 ? per : 1));
-  MRAG_LAUNCH(ip_attn_folded_kernel, dim3(gx, (unsigned)((H + HG - 1) / HG), (unsigned)(B / kv_batch_div)), dim3(256), lds, (hipStream_t)stream, p);
-  MRAG_LAUNCH_CHECK();
+  const int rc = launch_dyn_lds(ip_attn_folded_kernel, dim3(gx, (unsigned)((H + HG - 1) / HG), (unsigned)(B / kv_batch_div)), dim3(256), lds, (hipStream_t)stream, p);
+  if (rc != MRAG_OK) return rc;
   MRAG_COUNT(MRAG_K_IP_ATTN_FOLDED);
   return MRAG_OK;
 }

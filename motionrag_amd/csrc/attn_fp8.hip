@@ -25,8 +25,6 @@
 #include "attn_common.h"
 #include "../../include/mrag_hip.h"
 
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-
 namespace {
 
 constexpr int KT = 128;               // keys per LDS stage (two 64-key sub-tiles)
@@ -41,15 +39,6 @@ struct Fp8P {
   uint8_t* q8; uint8_t* k8; uint8_t* v8;
   unsigned* amax;        // [B * H][4]: fp32 bit patterns of max |Q|, |K|, |V| (atomicMax on the bits)
 };
-
-// largest e with amax * 2^e <= 448 (e4m3's largest finite value), clamped; amax == 0 -> 0
-__device__ __forceinline__ int pow2_fit(float amax) {
-  if (!(amax > 0.f)) return 0;
-  int e = (int)floorf(log2f(448.0f / amax));
-  if (ldexpf(amax, e) > 448.0f) --e;
-  if (ldexpf(amax, e + 1) <= 448.0f) ++e;
-  return e < -60 ? -60 : (e > 60 ? 60 : e);
-}
 
 __global__ __launch_bounds__(256) void amax_kernel(const AttnP p, unsigned* amax) {
   const int which = blockIdx.z, bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
@@ -70,11 +59,6 @@ __global__ __launch_bounds__(256) void amax_kernel(const AttnP p, unsigned* amax
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) { const unsigned t = __shfl_xor(m, o); m = t > m ? t : m; }
   if ((threadIdx.x & 63) == 0 && m) atomicMax(amax + bh * 4 + which, m);
-}
-
-__device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d) {
-  unsigned r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0u, false);
-  return __builtin_amdgcn_cvt_pk_fp8_f32(c, d, r, true);
 }
 
 // one workgroup = 64 rows x 64 features of Q, K or V of one (b, h): thread t holds row t / 4, features 16 (t % 4) .. + 15
@@ -355,10 +339,8 @@ extern "C" int mrag_attn_fwd_fp8(void* stream, const mrag_attn_args* a) {
   MRAG_LAUNCH(quant_kernel, dim3((smax + 63) / 64, (unsigned)bh, 3), dim3(256), 0, s, fp);
   MRAG_LAUNCH_CHECK();
   const size_t lds = NS8 * STAGE;
-  e = hipFuncSetAttribute((const void*)attn8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  MRAG_LAUNCH(attn8_kernel, dim3(p.n_qtiles * (unsigned)bh), dim3(512), lds, s, fp);
-  MRAG_LAUNCH_CHECK();
+  const int rc = launch_dyn_lds(attn8_kernel, dim3(p.n_qtiles * (unsigned)bh), dim3(512), lds, s, fp);
+  if (rc != MRAG_OK) return rc;
   MRAG_COUNT(MRAG_K_ATTN_FP8);
   return MRAG_OK;
 }

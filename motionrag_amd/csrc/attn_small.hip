@@ -115,11 +115,8 @@ template <int D>
 int launch_small(hipStream_t s, const SmallP& p) {
   const size_t lds = (size_t)p.Skv * D * 2 * 2;
   if (lds > 128 * 1024) return MRAG_ENOTSUP;
-  auto kfn = attn_small_kernel<D>;
-  const hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  MRAG_LAUNCH(kfn, dim3((unsigned)(p.B * p.H)), dim3(256), lds, s, p);
-  MRAG_LAUNCH_CHECK();
+  const int rc = launch_dyn_lds(attn_small_kernel<D>, dim3((unsigned)(p.B * p.H)), dim3(256), lds, s, p);
+  if (rc != MRAG_OK) return rc;
   MRAG_COUNT(MRAG_K_ATTN_SMALL);
   return MRAG_OK;
 }

@@ -13,6 +13,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+typedef __attribute__((ext_vector_type(8))) int i32x8;      // one fp8 MFMA A/B fragment (8 VGPRs)
 
 __device__ __forceinline__ float bf2f(bf16_t x) { return __uint_as_float(((unsigned)x) << 16); }
 // plain cast: hipcc emits v_cvt_pk_bf16_f32 (round-to-nearest-even, NaN preserved)
@@ -79,6 +80,20 @@ __device__ __forceinline__ void geglu4(float (&v)[4], const float (&g)[4]) {
 }
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
 
+// e4m3 quantisation (attn_fp8.hip, gemm_fp8.hip)
+// largest e with amax * 2^e <= 448 (e4m3's largest finite value), clamped; amax == 0 -> 0
+__device__ __forceinline__ int pow2_fit(float amax) {
+  if (!(amax > 0.f)) return 0;
+  int e = (int)floorf(log2f(448.0f / amax));
+  if (ldexpf(amax, e) > 448.0f) --e;
+  if (ldexpf(amax, e + 1) <= 448.0f) ++e;
+  return e < -60 ? -60 : (e > 60 ? 60 : e);
+}
+__device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d) {
+  unsigned r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0u, false);
+  return __builtin_amdgcn_cvt_pk_fp8_f32(c, d, r, true);
+}
+
 // async global -> LDS copy of 16 bytes per lane; LDS destination is
 // wave-uniform base + lane*16 (cdna_hip_programming.md section 5 caveat).
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
@@ -123,3 +138,20 @@ extern unsigned long long mrag_dispatch_table[];
     (void)hipGetLastError();        \
     hipLaunchKernelGGL(__VA_ARGS__); \
   } while (0)
+
+// a kernel that needs more dynamic LDS than the default limit: raise the limit, launch, return the launch's status (hipSuccess = MRAG_OK = 0).
+// hipGetLastError() is per-thread and sticky across unrelated runtime calls, so it is cleared in front of the launch (MRAG_LAUNCH).
+namespace {
+template <class P>
+inline int launch_dyn_lds(void (*kernel)(P), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const P& params) {
+  const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  if (e != hipSuccess) return (int)e;
+  MRAG_LAUNCH(kernel, grid, block, lds_bytes, stream, params);
+  return (int)hipGetLastError();
+}
+}  // namespace
+
+// A launcher that one unit of a kernel family defines and another calls.  The families' parameter blocks (GemmP, TopkP, ..) sit in the unnamed namespace (they
+// are part of every kernel's mangled name), and a C++ function whose signature names such a type is local to its unit: C linkage is the form that crosses
+// units.  Hidden: none of them belongs to the library's ABI.
+#define MRAG_FAMILY_LAUNCHER extern "C" __attribute__((visibility("hidden"))) int

@@ -7,7 +7,7 @@
 //   gemm_k320.hip    K = 320, weight in registers (launch_k320)
 //   gemm_skinny.hip  few rows, K split over the waves (launch_skinny)
 // Here: the kernel parameter block, the epilogue arithmetic that more than one family uses, the tile-choice predicates of the GEMM and the convolution
-// dispatch, the launch helper and the family launchers' declarations.
+// dispatch and the family launchers' declarations (the launch helper, launch_dyn_lds, is common.h's).
 #pragma once
 #include <type_traits>
 #include "common.h"
@@ -124,16 +124,6 @@ inline bool rows_16B_aligned(const void* C, long long ldc, const void* resid, lo
 // m-tiles per group of the logical tile order (gemm_tile, tile_coords): bits 8..15 of the tuning word, 4 unless set
 inline int group_m_of(int tuning) { return ((tuning >> 8) & 0xff) ? ((tuning >> 8) & 0xff) : 4; }
 
-// a kernel that needs more dynamic LDS than the default limit: raise the limit, launch, return the launch's status (hipSuccess = MRAG_OK = 0).
-// hipGetLastError() is per-thread and sticky across unrelated runtime calls, so it is cleared in front of the launch (MRAG_LAUNCH).
-template <class P>
-inline int launch_dyn_lds(void (*kernel)(P), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const P& params) {
-  const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  if (e != hipSuccess) return (int)e;
-  MRAG_LAUNCH(kernel, grid, block, lds_bytes, stream, params);
-  return (int)hipGetLastError();
-}
-
 // UNet widths are multiples of 320: N = 320 / 640 / 960 wastes 38 / 17 / 6 % of a 256-wide tile grid, nothing of a 320-wide one
 inline bool wide_n_pays(long long N, int tuning = 0) {
   if (tuning & MRAG_GEMM_TUNE_NO_WIDE) return false;
@@ -218,10 +208,8 @@ enum { TILE_256x256_W16, TILE_128x128, TILE_256x320, TILE_256x256 };
 
 }  // namespace
 
-// The family launchers, one per unit.  GemmP stays in the unnamed namespace (it is part of every kernel's mangled name), and a C++ function whose signature
-// names such a type is local to its unit: C linkage is the form that crosses units.  Hidden: none of them belongs to the library's ABI.
-#define MRAG_GEMM_LAUNCHER extern "C" __attribute__((visibility("hidden"))) int
-MRAG_GEMM_LAUNCHER launch_tiled(hipStream_t s, const GemmP& p, int epi, int tile, const SkPlan* sk);   // gemm_tiled.hip; sk: a stream-K plan (TILE_256x256 only) or null
-MRAG_GEMM_LAUNCHER launch_w4(hipStream_t s, const GemmP& p, int epi);                                  // gemm_w4.hip
-MRAG_GEMM_LAUNCHER launch_k320(hipStream_t s, const GemmP& p, int epi);                                // gemm_k320.hip
-MRAG_GEMM_LAUNCHER launch_skinny(hipStream_t s, const GemmP& p, int epi);                              // gemm_skinny.hip
+// The family launchers, one per unit (MRAG_FAMILY_LAUNCHER, common.h: GemmP is part of their signatures).
+MRAG_FAMILY_LAUNCHER launch_tiled(hipStream_t s, const GemmP& p, int epi, int tile, const SkPlan* sk);   // gemm_tiled.hip; sk: a stream-K plan (TILE_256x256 only) or null
+MRAG_FAMILY_LAUNCHER launch_w4(hipStream_t s, const GemmP& p, int epi);                                  // gemm_w4.hip
+MRAG_FAMILY_LAUNCHER launch_k320(hipStream_t s, const GemmP& p, int epi);                                // gemm_k320.hip
+MRAG_FAMILY_LAUNCHER launch_skinny(hipStream_t s, const GemmP& p, int epi);                              // gemm_skinny.hip

@@ -1,7 +1,7 @@
 // gemm_fp8.hip -- the opt-in e4m3 path of the DiT's four large linears (attn_processor.py:209-211,276 and diffusers CogVideoXBlock FF):
 //
-//   mrag_quant_rows_e4m3   x [M, K] bf16 -> x8 [M, K] OCP e4m3fn bytes + exp [M] int32: per row e = pow2_fit(amax_row) (the function of that name in
-//                          attn_fp8.hip), x8 = rne_e4m3(x * 2^e).  One pass: a row is read once (kept in registers), its maximum reduced in the wave /
+//   mrag_quant_rows_e4m3   x [M, K] bf16 -> x8 [M, K] OCP e4m3fn bytes + exp [M] int32: per row e = pow2_fit(amax_row) (common.h: the function
+//                          attn_fp8.hip scales with), x8 = rne_e4m3(x * 2^e).  One pass: a row is read once (kept in registers), its maximum reduced in the wave /
 //                          workgroup, written once.  Activations every call, weights ([N, K]: per output channel) once.
 //   mrag_gemm_fp8          C[m, n] = epilogue(2^-(ea[m] + ew[n]) * sum_k A8[m, k] W8[n, k] + bias[n]) on v_mfma_scale_f32_32x32x64_f8f6f4 (twice the bf16
 //                          MFMA rate, half the LDS / DMA bytes).  The row exponents ride the instruction's E8M0 scale operands (127 - e per lane: a lane's
@@ -18,28 +18,12 @@
 // in the accumulator layout, rounded to bf16, the residual added in the row layout), so C may alias resid.
 #include "gemm_common.h"
 
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-
 // host-side relaxed launch counters (mrag_fp8_launch_counts): slot 0 the GEMM, slot 1 the row quantiser
 static unsigned long long g_fp8_launches[2];
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ row quantiser
-// largest e with amax * 2^e <= 448 (e4m3's largest finite value), clamped; amax == 0 -> 0 (pow2_fit of attn_fp8.hip)
-__device__ __forceinline__ int pow2_fit(float amax) {
-  if (!(amax > 0.f)) return 0;
-  int e = (int)floorf(log2f(448.0f / amax));
-  if (ldexpf(amax, e) > 448.0f) --e;
-  if (ldexpf(amax, e + 1) <= 448.0f) ++e;
-  return e < -60 ? -60 : (e > 60 ? 60 : e);
-}
-
-__device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d) {
-  unsigned r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0u, false);
-  return __builtin_amdgcn_cvt_pk_fp8_f32(c, d, r, true);
-}
-
 __device__ __forceinline__ unsigned absmax8(unsigned m, const u32x4 v) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {

@@ -42,7 +42,7 @@ typedef struct { double d; int32_t r; } cand_t;
 
 static int cand_less(cand_t a, cand_t b) { return a.d < b.d || (a.d == b.d && a.r < b.r); }
 
-/* mode 0: the fp32 evaluation order the HIP kernel uses (motionrag_amd/csrc/topk.hip): 16 interleaved fmaf chains -- chain l
+/* mode 0: the fp32 evaluation order the HIP kernel uses (motionrag_amd/csrc/topk_scan.hip): 16 interleaved fmaf chains -- chain l
  * runs over k = 64 j + 4 l + c (j = 0.., c = 0..3) -- folded by a fixed pairwise tree p[l] += p[l ^ 8], ^4, ^2, ^1.  (A SIMD
  * flat scan such as lance's also keeps per-lane partial sums and adds them horizontally at the end; the exact lane count of
  * lance's kernels is not pinned, see the header.) */

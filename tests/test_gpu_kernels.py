@@ -788,7 +788,7 @@ def test_topk_baseline_size(hip):
 
 
 def _fanout_shape(N, Q):
-    """which launch shape the fan-out form's plan takes (topk.hip plan_dense): 'one' launch (the dense grid is resident at once), 'two' (dense scores, then the
+    """which launch shape the fan-out form's plan takes (plan_dense in topk.hip; the kernels are topk_dense.hip's and topk_mfma.hip's): 'one' launch (the dense grid is resident at once), 'two' (dense scores, then the
     finishing launch) or 'stream' (pre-pass, streaming kernel with in-kernel lists, merge)"""
     blocks, qtiles = -(-N // 128), -(-Q // 32)
     if blocks > 512 or Q * blocks * 128 > (16 << 20):
