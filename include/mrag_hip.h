@@ -289,8 +289,10 @@ typedef struct mrag_attn_args {
 } mrag_attn_args;
 enum { MRAG_ATTN_TUNE_NO_TINY = 1,   /* never take the <= 16-key one-wave-per-pair kernel          */
                                      /* 2, 4: retired (intra-wave pipelined tile, 4-wave long-sequence workgroups: measured slower, code pruned in round 3) */
-       MRAG_ATTN_TUNE_LEGACY = 8 };  /* long unmasked sequences through the 32x32x16 kernel (the masked / biased path's kernel, kept
+       MRAG_ATTN_TUNE_LEGACY = 8,    /* long unmasked sequences through the 32x32x16 kernel (the masked / biased path's kernel, kept
                                         selectable so tests can compare the two families on one input)                          */
+       MRAG_ATTN_TUNE_FP8_QUANT_ONLY = 16 };   /* mrag_attn_joint_fwd_fp8 only: return after amax + quantise, before the attention kernel (nothing is
+                                                  written to O, nothing counted) -- how tools/attn_fp8_joint_measure.py times the two halves of a call */
                                      /* every other bit: retired A/B variants (ABI 8 removed 128..1024: the attn16 workgroup-shape variants and
                                         the attn32 family now live in tools/exp/ with their measurement tables)                  */
 
@@ -311,6 +313,21 @@ int64_t mrag_attn_workspace_bytes(int32_t B, int32_t H, int32_t Sq, int32_t Skv)
  * opt-in, never used for the bf16 headline workload.                                                                                  */
 int64_t mrag_attn_fp8_workspace_bytes(int32_t B, int32_t H, int32_t Sq, int32_t Skv);
 int mrag_attn_fwd_fp8(void* stream, const mrag_attn_args* args);
+
+/* The same fp8 path for the CogVideoX DiT's joint [text ; video] attention (attn_processor.py:233-235; opt-in through
+ * cogvideox.set_attention_precision): any key count and a pre-scaled Q.  Argument struct, alignment rules, fused resid / out_scale and
+ * the REQUIRED workspace as mrag_attn_fwd_fp8; MRAG_ENOTSUP for a mask, a bias, kv_batch_div != 1 or Skv < 512; every Skv >= 512 and
+ * either value of q_prescaled are taken (q_prescaled: Q carries scale * log2 e already, the quantiser's multiplier is 1).
+ * K8 / V8 are laid out for Skv rounded up to 128; the padding key rows are written as zero bytes on every call (the workspace may hold
+ * anything) and masked in the last 128-key stage before the softmax sees them: they add exactly nothing to O or to a row's sum and
+ * cannot move a row's centre.  Skv % 128 == 0 with q_prescaled == 0 launches the kernels of mrag_attn_fwd_fp8: bit-identical output.
+ * mrag_attn_joint_fp8_workspace_bytes(B, H, Sq, Skv) == mrag_attn_fp8_workspace_bytes(B, H, Sq, Skv rounded up to 128).
+ * Precision (tests/test_gpu_fp8_joint_attention.py, tolerances of tests/test_gpu_fp8.py): operands carry 3 mantissa bits; a row is
+ * centred on the maximum of its FIRST 64 keys -- text tokens in the joint sequence -- and only ever re-centres upward, when a 64-key sum
+ * of P' reaches e4m3's range, so a probability more than about 2^-11 below the row's centre is dropped (P' = 4 at the centre, e4m3's
+ * smallest subnormal is 2^-9).  The bf16 kernel remains the reference precision.  Counted under MRAG_K_ATTN_FP8.                      */
+int64_t mrag_attn_joint_fp8_workspace_bytes(int32_t B, int32_t H, int32_t Sq, int32_t Skv);
+int mrag_attn_joint_fwd_fp8(void* stream, const mrag_attn_args* args);
 
 /* ------------------------------------------------------------------------ */
 /* Motion-adapter branch with the query projection folded into the keys:      */

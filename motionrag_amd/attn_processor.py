@@ -101,14 +101,24 @@ class _FusedWeights:
         self._cache.clear()
 
 
+def _joint_sdpa(q, k, v, fp8_attn: bool):
+    """attn_processor.py:233-235 on a Q that carries scale * log2 e: the bf16 kernel, or (cogvideox.set_attention_precision) the e4m3 kernel on the shapes it
+    takes -- short toy sequences stay bf16, as in the UNets.  q / k / v are strided views; neither kernel needs a copy."""
+    if fp8_attn and ops.fp8_joint_attention_supported(q.shape[1], k.shape[1]):
+        return ops.joint_attention_fp8(q, k, v, q_prescaled=True)
+    return ops.attention(q, k, v, q_prescaled=True)
+
+
 def joint_attention_core(attn, proc, x: torch.Tensor, text_len: int, rope, ip_hidden_states: Optional[torch.Tensor], scale: float, sp=None,
-                         fp8_qkv: bool = False):
+                         fp8_qkv: bool = False, fp8_attn: bool = False):
     """attn_processor.py:209-273 on the joint [text ; video] sequence x [B, S, D] (bf16, contiguous).
     Returns the attention output BEFORE to_out: `o + scale * ip_attention(to_q_ip(o))`.
     `sp` (dist.SequenceParallel): x holds only this rank's rows (text_len / rope already local); K and V rows of all ranks are
     all-gathered after qk-norm + RoPE, everything else stays local.
     `fp8_qkv` (cogvideox.set_linear_precision): the fused QKV projection on the e4m3 GEMM, then the stand-alone qk-norm + RoPE kernel; ignored
-    under `sp` (the sharded projection's [K | V]-first order lives in the bf16 GEMM's fused epilogue)."""
+    under `sp` (the sharded projection's [K | V]-first order lives in the bf16 GEMM's fused epilogue).
+    `fp8_attn` (cogvideox.set_attention_precision): the joint attention itself on the e4m3 kernel (ops.joint_attention_fp8), on every path, sharded included;
+    independent of `fp8_qkv`.  The motion branch stays bf16."""
     B, S, D = x.shape
     H = attn.heads
     fw = proc._fused
@@ -128,7 +138,7 @@ def joint_attention_core(attn, proc, x: torch.Tensor, text_len: int, rope, ip_hi
             raise NotImplementedError("RoPE on Q only (is_cross_attention=True) is not used by CogVideoX attn1")
     nq, nk = getattr(attn, "norm_q", None), getattr(attn, "norm_k", None)
     if sp is not None:
-        o = _sharded_attention(attn, x, wqkv, bqkv, H, nq, nk, cos, sin, text_len, sp)
+        o = _sharded_attention(attn, x, wqkv, bqkv, H, nq, nk, cos, sin, text_len, sp, fp8_attn)
         return _motion_branch(attn, proc, o, ip_hidden_states, scale)
     if fp8_qkv:
         # the concatenated weight quantised once per output channel; the projection with a plain epilogue, then norm_q / norm_k + RoPE in place
@@ -138,18 +148,18 @@ def joint_attention_core(attn, proc, x: torch.Tensor, text_len: int, rope, ip_hi
         ops.qknorm_rope_(qkv, H, nq.weight if nq is not None else None, nq.bias if nq is not None else None, nk.weight if nk is not None else None,
                          nk.bias if nk is not None else None, cos, sin, text_len, eps=nq.eps if nq is not None else 1e-6, q_premul=ops.LOG2E * 64 ** -0.5)
         q5 = qkv.view(B, S, 3, H, 64)
-        o = ops.attention(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], q_prescaled=True)
+        o = _joint_sdpa(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], fp8_attn)
         return _motion_branch(attn, proc, o, ip_hidden_states, scale)
     # :209-211 + :220-231 in ONE GEMM: the projection's epilogue applies norm_q / norm_k and the rotary embedding to the Q and K thirds
     qkv = ops.qkv_linear_qknorm_rope(x, wqkv, bqkv, H, nq.weight if nq is not None else None, nq.bias if nq is not None else None,
                                      nk.weight if nk is not None else None, nk.bias if nk is not None else None, cos, sin, text_len,
                                      eps=nq.eps if nq is not None else 1e-6, q_premul=ops.LOG2E * 64 ** -0.5)
     q5 = qkv.view(B, S, 3, H, 64)
-    o = ops.attention(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], q_prescaled=True)   # :233-237
+    o = _joint_sdpa(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], fp8_attn)   # :233-237
     return _motion_branch(attn, proc, o, ip_hidden_states, scale)
 
 
-def _sharded_attention(attn, x, wqkv, bqkv, H, nq, nk, cos, sin, text_len, sp):
+def _sharded_attention(attn, x, wqkv, bqkv, H, nq, nk, cos, sin, text_len, sp, fp8_attn=False):
     """Tier-2 sequence sharding: x holds this rank's rows.  The [K | V] thirds are projected FIRST (norm_k + RoPE in the GEMM
     epilogue) straight into this rank's row range of the gathered buffer's layout -- per sample a contiguous [s_loc, 2 D] block -- and their
     all-gather is started asynchronously (RCCL runs it on its own stream over xGMI); the Q third is projected while the gather is in
@@ -163,11 +173,11 @@ def _sharded_attention(attn, x, wqkv, bqkv, H, nq, nk, cos, sin, text_len, sp):
     except NotImplementedError:          # toy sizes (128x128 GEMM tiles carry no fused epilogue): whole projection + the norm / RoPE kernel, then split
         qkv = ops.qkv_linear_qknorm_rope(x, wqkv, bqkv, H, gq, bq, gk, bk, cos, sin, text_len, **qn)
         g = sp.all_gather_rows_async(qkv[..., D:].contiguous()).wait().view(B, -1, 2, H, 64)
-        return ops.attention(qkv[..., :D].unflatten(-1, (H, 64)), g[:, :, 0], g[:, :, 1], q_prescaled=True)
+        return _joint_sdpa(qkv[..., :D].unflatten(-1, (H, 64)), g[:, :, 0], g[:, :, 1], fp8_attn)
     pending = sp.all_gather_rows_async(kv)                                        # -> [B, S_total, 2 D], rank-major rows == global row order
     q = ops.qkv_linear_qknorm_rope(x, wqkv[:D], bqkv[:D] if bqkv is not None else None, H, gq, bq, gk, bk, cos, sin, text_len, first=0, **qn)    # [B, s_loc, D]
     g = pending.wait().view(B, -1, 2, H, 64)
-    return ops.attention(q.view(B, S, H, 64), g[:, :, 0], g[:, :, 1], q_prescaled=True)
+    return _joint_sdpa(q.view(B, S, H, 64), g[:, :, 0], g[:, :, 1], fp8_attn)
 
 
 def _motion_branch(attn, proc, o, ip_hidden_states, scale):

@@ -113,10 +113,22 @@ def set_linear_precision(model: "CogVideoXTransformer3DModel", precision: str = 
     return model
 
 
+def set_attention_precision(model: "CogVideoXTransformer3DModel", precision: str = "bf16") -> "CogVideoXTransformer3DModel":
+    """'bf16' (the reference's precision: every call exactly where it is without this option) or 'fp8': the joint [text ; video] attention of every
+    CogVideoXBlock (attn_processor.py:233-235) runs on the e4m3 MFMA kernel (ops.joint_attention_fp8) where ops.fp8_joint_attention_supported holds -- 512
+    keys or more; shorter toy sequences stay on the bf16 kernel, as in the UNets (dynamicrafter.set_attention_precision) -- sharded or not.  Independent of
+    set_linear_precision: any combination works.  The motion branch is bf16 either way."""
+    if precision not in ("bf16", "fp8"):
+        raise ValueError("precision must be 'bf16' or 'fp8'")
+    model.attention_precision = precision
+    return model
+
+
 class CogVideoXTransformer3DModel(nn.Module):
     """CogVideoX-5B-I2V DiT (rotary + learned positional embedding flavour)."""
     linear_precision = "bf16"          # set_linear_precision
     linear_fp8_sites = frozenset()
+    attention_precision = "bf16"       # set_attention_precision
 
     def __init__(self, num_layers=42, num_attention_heads=48, attention_head_dim=64, in_channels=32, out_channels=16, time_embed_dim=512,
                  text_embed_dim=4096, max_text_seq_length=226, patch_size=2, sample_frames=13, sample_height=60, sample_width=90,
@@ -261,7 +273,7 @@ class CogVideoXTransformer3DModel(nn.Module):
             nh = ops.layernorm(x, blk.norm1.norm.weight, blk.norm1.norm.bias, cfg["norm_eps"], shift0=chunk(2 * i, 3), scale0=chunk(2 * i, 4),
                                shift1=chunk(2 * i, 0), scale1=chunk(2 * i, 1), rows_per_batch=S, split=Lt, mod_stride=ms)
             scale = proc.scale[0] if ip is not None else 0.0
-            o = joint_attention_core(blk.attn1, proc, nh, Lt, rope, ip, scale, sp=sp, fp8_qkv="qkv" in fp8)
+            o = joint_attention_core(blk.attn1, proc, nh, Lt, rope, ip, scale, sp=sp, fp8_qkv="qkv" in fp8, fp8_attn=self.attention_precision == "fp8")
             site_linear("to_out", i, o, blk.attn1.to_out[0], out=x, epilogue=ops.EPI_GATE_RESID, resid=x,
                         gate0=chunk(2 * i, 5), gate1=chunk(2 * i, 2), rows_per_batch=S, split=Lt, gate_stride=ms)
             nh = ops.layernorm(x, blk.norm2.norm.weight, blk.norm2.norm.bias, cfg["norm_eps"], shift0=chunk(2 * i + 1, 3),

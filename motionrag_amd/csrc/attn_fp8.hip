@@ -18,6 +18,10 @@
 //      Round 6: the row sums ride the matrix pipe -- l^T = ONES . P8^T, one more MFMA per 64 keys whose every output register is the lane's complete tile sum
 //      (of the e4m3 values that multiply V) -- instead of 32 v_add per lane and sub-tile: the loop was bound by vector issue (32 v_exp + 32 v_add + 16 v_cvt_pk per
 //      four 64-cycle MFMAs), now it issues 32 v_exp + 16 v_cvt_pk against five MFMAs; waves switch priority by phase as in attn16.hip.
+//   mrag_attn_joint_fwd_fp8 (the CogVideoX DiT's joint [text ; video] attention, attn_processor.py:233-235; opt-in, cogvideox.set_attention_precision): the same three
+//   kernels for ANY key count >= 512 and a Q that already carries scale * log2 e.  RAGGED instantiations: K8 / V8 are laid out for Skv rounded up to 128, the padding
+//   key rows written as zero bytes on every call, and the last 128-key stage masks their scores before the softmax sees them (sub_tile's TAIL variant).  Whole stages
+//   launch the <false> instantiations, the code mrag_attn_fwd_fp8 runs.
 // Operand maps were measured, not assumed: tools/exp/fp8_layout_probe.hip -> A[row = l & 31][k = 32 (l >> 5) + byte], B likewise, the lane's
 // scale byte applies to its own 32 k's (profiles/r2_fp8_layout_probe.txt).
 // Precision: e4m3 carries 3 mantissa bits: expect ~3-6 % relative Frobenius error against fp32 attention (tests state the tolerance);
@@ -32,6 +36,7 @@ constexpr int STAGE_K = KT * 64;      // 8 KB of K8
 constexpr int STAGE = 2 * STAGE_K;    // + 8 KB of V8
 constexpr int NS8 = 4;
 constexpr float kPShift = 2.0f;       // P' = 4 P: a re-centred row's 64-key tile sums to at most 256, below the trigger
+constexpr float kMasked8 = -1e30f;    // the log2-domain score of a padding key (ragged tail): v_exp_f32 gives exactly +0, and fp32 keeps it so under any `- delta`
 constexpr float kBig8 = 448.0f;       // a 64-key row sum of P' at or above e4m3's largest finite value -> some P' may not have been representable: re-centre
 
 struct Fp8P {
@@ -61,13 +66,19 @@ __global__ __launch_bounds__(256) void amax_kernel(const AttnP p, unsigned* amax
   if ((threadIdx.x & 63) == 0 && m) atomicMax(amax + bh * 4 + which, m);
 }
 
+constexpr int pad_keys(int skv) { return (skv + KT - 1) / KT * KT; }
+
 // one workgroup = 64 rows x 64 features of Q, K or V of one (b, h): thread t holds row t / 4, features 16 (t % 4) .. + 15
+// RAGGED (mrag_attn_joint_fwd_fp8): K8 / V8 are laid out for Skv rounded up to whole 128-key stages; key rows >= Skv are written as zero bytes on EVERY call
+// (the workspace is a shared grow-only buffer: stale bytes may be e4m3 NaNs) and no source row >= Skv is read
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void quant_kernel(const Fp8P fp) {
   __shared__ __attribute__((aligned(16))) uint8_t vt[64 * 64];
   const AttnP& p = fp.a;
   const int which = blockIdx.z, bh = blockIdx.y, b = bh / p.H, h = bh % p.H, tile = blockIdx.x;
   const int S = which == 0 ? p.Sq : p.Skv;
-  if (tile * 64 >= S) return;
+  const int SP = (RAGGED && which != 0) ? pad_keys(S) : S;            // rows of the destination layout
+  if (tile * 64 >= SP) return;
   const float aq = __uint_as_float(fp.amax[bh * 4 + 0]), ak = __uint_as_float(fp.amax[bh * 4 + 1]), av = __uint_as_float(fp.amax[bh * 4 + 2]);
   float mul;
   if (which == 0) mul = ldexpf(p.qscale, pow2_fit(aq * p.qscale));     // Q * (scale log2 e) * 2^y
@@ -76,8 +87,8 @@ __global__ __launch_bounds__(256) void quant_kernel(const Fp8P fp) {
   const int t = threadIdx.x, row = t >> 2, seg = t & 3, grow = tile * 64 + row;
   const bf16_t* src;
   if (which == 0) src = p.Q + (long long)b * p.q_sb + (long long)h * p.q_sh + (long long)(grow < S ? grow : S - 1) * p.q_ss;
-  else if (which == 1) src = p.K + (long long)b * p.k_sb + (long long)h * p.k_sh + (long long)grow * p.k_ss;
-  else src = p.V + (long long)b * p.v_sb + (long long)h * p.v_sh + (long long)grow * p.v_ss;
+  else if (which == 1) src = p.K + (long long)b * p.k_sb + (long long)h * p.k_sh + (long long)(RAGGED && grow >= S ? S - 1 : grow) * p.k_ss;
+  else src = p.V + (long long)b * p.v_sb + (long long)h * p.v_sh + (long long)(RAGGED && grow >= S ? S - 1 : grow) * p.v_ss;
   float f[16];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -88,11 +99,17 @@ __global__ __launch_bounds__(256) void quant_kernel(const Fp8P fp) {
       f[8 * i + 2 * j + 1] = __uint_as_float(v[j] & 0xffff0000u) * mul;
     }
   }
+  if constexpr (RAGGED) {
+    if (which != 0 && grow >= S) {                                   // a padding key: +0.0 in every feature -> zero bytes in K8 and in V8's transposed tile
+#pragma unroll
+      for (int i = 0; i < 16; ++i) f[i] = 0.f;
+    }
+  }
   if (which != 2) {
     const u32x4 o = {pack4_fp8(f[0], f[1], f[2], f[3]), pack4_fp8(f[4], f[5], f[6], f[7]), pack4_fp8(f[8], f[9], f[10], f[11]), pack4_fp8(f[12], f[13], f[14], f[15])};
-    uint8_t* dst = (which == 0 ? fp.q8 : fp.k8) + ((long long)bh * S + grow) * 64;
+    uint8_t* dst = (which == 0 ? fp.q8 : fp.k8) + ((long long)bh * SP + grow) * 64;
     const int chunk = which == 0 ? seg : (seg ^ ((row >> 2) & 3));     // K8: LDS bank swizzle baked into the row
-    if (grow < S) *(u32x4*)(dst + chunk * 16) = o;
+    if (grow < SP) *(u32x4*)(dst + chunk * 16) = o;
     return;
   }
   // V: transpose the 64-key tile to [d][slot]; slot of key k: lane half hh = (k >> 2) & 1 takes bytes 32 hh .., block k >> 5 its 16-byte half,
@@ -107,7 +124,7 @@ __global__ __launch_bounds__(256) void quant_kernel(const Fp8P fp) {
     vt[d * 64 + pos] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
   }
   __syncthreads();
-  *(u32x4*)(fp.v8 + ((long long)bh * S + tile * 64) * 64 + t * 16) = *(const u32x4*)(vt + t * 16);
+  *(u32x4*)(fp.v8 + ((long long)bh * SP + tile * 64) * 64 + t * 16) = *(const u32x4*)(vt + t * 16);
 }
 
 __device__ __forceinline__ float half_swap_max8(float v) {
@@ -115,7 +132,10 @@ __device__ __forceinline__ float half_swap_max8(float v) {
   return max3_asm(__uint_as_float(sw[0]), __uint_as_float(sw[1]), __uint_as_float(sw[1]));
 }
 
-// 8 waves x 32 query rows; Skv % 128 == 0; no mask; K/V batch == Q batch.
+// 8 waves x 32 query rows; no mask; K/V batch == Q batch.  RAGGED = false: Skv % 128 == 0.
+// RAGGED = true (the DiT's joint sequence): K8 / V8 hold Skv rounded up to whole stages, zero past Skv (quant_kernel<true>); the LAST stage runs the masking
+// variant of sub_tile, every stage before it the same code as RAGGED = false.
+template <bool RAGGED>
 __global__ __launch_bounds__(512, 4) void attn8_kernel(const Fp8P fp) {
   const AttnP& p = fp.a;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -146,12 +166,13 @@ __global__ __launch_bounds__(512, 4) void attn8_kernel(const Fp8P fp) {
   const i32x8 qf = *(const i32x8*)(fp.q8 + ((long long)bh * p.Sq + qc) * 64 + hh * 32);
 
   // LDS-DMA: a stage = 128 keys = 8 KB of K8 + 8 KB of V8, both stored in their LDS image order: 16 linear 1-KiB pieces, 2 per wave
-  const char* k8 = (const char*)fp.k8 + (long long)bh * p.Skv * 64;
-  const char* v8 = (const char*)fp.v8 + (long long)bh * p.Skv * 64;
+  const int skvp = RAGGED ? pad_keys(p.Skv) : p.Skv;
+  const char* k8 = (const char*)fp.k8 + (long long)bh * skvp * 64;
+  const char* v8 = (const char*)fp.v8 + (long long)bh * skvp * 64;
   const unsigned loff = wave * 1024 + lane * 16;
   const unsigned lds0 = (unsigned)(size_t)smem;
-  const int nt = p.Skv / KT;
-  auto issue_kv = [&](int stage, int t) {
+  const int nt = skvp / KT;
+  auto issue_kv = [&](int stage, int t) __attribute__((always_inline)) {
     const int tt = t < nt ? t : nt - 1;                 // prefetches past the end re-read the last tile (never consumed)
     glds16_sbase(k8 + (long long)tt * STAGE_K, loff, lds0 + stage * STAGE + wave * 1024);
     glds16_sbase(v8 + (long long)tt * STAGE_K, loff, lds0 + stage * STAGE + STAGE_K + wave * 1024);
@@ -175,8 +196,20 @@ __global__ __launch_bounds__(512, 4) void attn8_kernel(const Fp8P fp) {
 #pragma unroll
   for (int i = 0; i < D; ++i) issue_kv(i, i);
 
-  auto sub_tile = [&](int t, int sub, auto stage_c, auto sub_c) {
+  // TAIL (the last stage of RAGGED only): the sub-tile holds `real` < 64 keys of the sequence, or none.  Register i of s0 / s1 in lane (query r32, half hh) is
+  // key 32 blk + (i & 3) + 8 (i >> 2) + 4 hh of the sub-tile (blk 0 = s0, 1 = s1): the inverse of quant_kernel's `slot`, which puts key k at byte
+  // 32 ((k >> 2) & 1) + 16 (k >> 5) + (k & 3) + 4 ((k & 31) >> 3) of the lane pair's 64 P' bytes, byte 16 blk + i of half hh being register i of s<blk>.
+  auto sub_tile = [&](int t, int sub, auto stage_c, auto sub_c, auto tail_c) __attribute__((always_inline)) {
     constexpr int OFF = decltype(stage_c)::value * STAGE + decltype(sub_c)::value * 4096;
+    constexpr bool TAIL = decltype(tail_c)::value;
+    [[maybe_unused]] int lim = 0;                                                      // this lane's keys are real where 32 blk + (i & 3) + 8 (i >> 2) < lim
+    if constexpr (TAIL) {
+      const int real = p.Skv - (t * KT + sub * 64);
+      if (real <= 0) return;                                          // all padding (Skv % 128 <= 64, second sub-tile): l, o0, o1, m stay as they are
+      lim = real - 4 * hh;
+    }
+    // the ragged stage sits in LDS slot t % 4, known only at run time: its byte offset rides in the fragment addresses (stage_c is 0 there)
+    const unsigned a0 = TAIL ? fa0 + (t & (NS8 - 1)) * STAGE : fa0, a1 = TAIL ? fa1 + (t & (NS8 - 1)) * STAGE : fa1;
     f32x16 s0, s1;
     bool recentre = (t == 0 && sub == 0);
     float tile_sum;
@@ -186,11 +219,20 @@ __global__ __launch_bounds__(512, 4) void attn8_kernel(const Fp8P fp) {
       asm volatile("ds_read_b128 %0, %4 offset:%6\n\tds_read_b128 %1, %5 offset:%6\n\tds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %5 offset:%7\n\t"
                    "s_waitcnt lgkmcnt(0)"
                    : "=&v"(ka[0]), "=&v"(ka[1]), "=&v"(kb[0]), "=&v"(kb[1])
-                   : "v"(fa0), "v"(fa1), "n"(OFF), "n"(OFF + 2048) : "memory");
+                   : "v"(a0), "v"(a1), "n"(OFF), "n"(OFF + 2048) : "memory");
       const i32x8 kf0 = {(int)ka[0][0], (int)ka[0][1], (int)ka[0][2], (int)ka[0][3], (int)ka[1][0], (int)ka[1][1], (int)ka[1][2], (int)ka[1][3]};
       const i32x8 kf1 = {(int)kb[0][0], (int)kb[0][1], (int)kb[0][2], (int)kb[0][3], (int)kb[1][0], (int)kb[1][1], (int)kb[1][2], (int)kb[1][3]};
       s0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(kf0, qf, negm, 0, 0, 0, scale_one, 0, scale_q);
       s1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(kf1, qf, negm, 0, 0, 0, scale_one, 0, scale_q);
+      if constexpr (TAIL) {
+        // padding keys: exp2 of this is exactly 0 (before and after a re-centre's `- delta`), so they add nothing to O or l, and at least one real key
+        // (real >= 1) carries the re-centre maximum
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          if ((i & 3) + 8 * (i >> 2) >= lim) s0[i] = kMasked8;
+          if (32 + (i & 3) + 8 * (i >> 2) >= lim) s1[i] = kMasked8;
+        }
+      }
       if (recentre) {
         // plain fmaxf, NOT the inline-asm v_max3 helper: hipcc pads the MFMA -> VALU read hazard (16-pass MFMA: many wait states) only for
         // instructions it can see; an asm statement reading s0 / s1 straight after the MFMAs read stale registers (found the hard way)
@@ -239,31 +281,34 @@ __global__ __launch_bounds__(512, 4) void attn8_kernel(const Fp8P fp) {
     asm volatile("ds_read_b128 %0, %4 offset:%6\n\tds_read_b128 %1, %5 offset:%6\n\tds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %5 offset:%7\n\t"
                  "s_waitcnt lgkmcnt(0)"
                  : "=&v"(va[0]), "=&v"(va[1]), "=&v"(vb[0]), "=&v"(vb[1])
-                 : "v"(fa0), "v"(fa1), "n"(OFF + STAGE_K), "n"(OFF + STAGE_K + 2048) : "memory");
+                 : "v"(a0), "v"(a1), "n"(OFF + STAGE_K), "n"(OFF + STAGE_K + 2048) : "memory");
     const i32x8 vf0 = {(int)va[0][0], (int)va[0][1], (int)va[0][2], (int)va[0][3], (int)va[1][0], (int)va[1][1], (int)va[1][2], (int)va[1][3]};
     const i32x8 vf1 = {(int)vb[0][0], (int)vb[0][1], (int)vb[0][2], (int)vb[0][3], (int)vb[1][0], (int)vb[1][1], (int)vb[1][2], (int)vb[1][3]};
     o0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(vf0, pb, o0, 0, 0, 0, scale_one, 0, scale_one);
     o1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(vf1, pb, o1, 0, 0, 0, scale_one, 0, scale_one);
     __builtin_amdgcn_s_setprio(1);
   };
-  auto iter = [&](int t, auto stage_c) {
+  auto iter_any = [&](int t, auto stage_c, auto tail_c) __attribute__((always_inline)) {
     constexpr int STG = decltype(stage_c)::value;
     wait_pair();
-    issue_kv((STG + D) % NS8, t + D);
+    if constexpr (!decltype(tail_c)::value) issue_kv((STG + D) % NS8, t + D);   // (the last stage has nothing left to prefetch; wait_pair counts stages issued, not this one)
     if (!wave_active) return;
-    sub_tile(t, 0, stage_c, std::integral_constant<int, 0>{});
-    sub_tile(t, 1, stage_c, std::integral_constant<int, 1>{});
+    sub_tile(t, 0, stage_c, std::integral_constant<int, 0>{}, tail_c);
+    sub_tile(t, 1, stage_c, std::integral_constant<int, 1>{}, tail_c);
   };
+  auto iter = [&](int t, auto stage_c) __attribute__((always_inline)) { iter_any(t, stage_c, std::false_type{}); };
+  const int nfull = RAGGED ? nt - 1 : nt;                             // stages whose 128 keys are all real
   int t = 0;
-  for (; t + NS8 <= nt; t += NS8) {
+  for (; t + NS8 <= nfull; t += NS8) {
     iter(t, std::integral_constant<int, 0>{});
     iter(t + 1, std::integral_constant<int, 1>{});
     iter(t + 2, std::integral_constant<int, 2>{});
     iter(t + 3, std::integral_constant<int, 3>{});
   }
-  if (t < nt) { iter(t, std::integral_constant<int, 0>{}); ++t; }
-  if (t < nt) { iter(t, std::integral_constant<int, 1>{}); ++t; }
-  if (t < nt) { iter(t, std::integral_constant<int, 2>{}); ++t; }
+  if (t < nfull) { iter(t, std::integral_constant<int, 0>{}); ++t; }
+  if (t < nfull) { iter(t, std::integral_constant<int, 1>{}); ++t; }
+  if (t < nfull) { iter(t, std::integral_constant<int, 2>{}); ++t; }
+  if constexpr (RAGGED) iter_any(nfull, std::integral_constant<int, 0>{}, std::true_type{});
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (!wave_active || qrow >= p.Sq) return;
 
@@ -302,14 +347,20 @@ extern "C" int64_t mrag_attn_fp8_workspace_bytes(int32_t B, int32_t H, int32_t S
   return (int64_t)(align256(bh * 16) + align256(bh * Sq * 64) + 2 * align256(bh * Skv * 64));
 }
 
-extern "C" int mrag_attn_fwd_fp8(void* stream, const mrag_attn_args* a) {
+namespace {
+
+// both entry points: `joint` lifts mrag_attn_fwd_fp8's two refusals (Skv % 128, q_prescaled) and adds none of its own
+int fwd_fp8(void* stream, const mrag_attn_args* a, bool joint) {
   if (!a || !a->Q || !a->K || !a->V || !a->O || !a->workspace) return MRAG_EINVAL;
   if (a->B <= 0 || a->H <= 0 || a->Sq <= 0 || a->Skv <= 0) return MRAG_EINVAL;
-  if (a->mask || a->kv_batch_div != 1 || a->Skv % KT != 0 || a->Skv < 4 * KT || a->q_prescaled) return MRAG_ENOTSUP;
+  if (a->mask || a->kv_batch_div != 1 || a->Skv < 4 * KT) return MRAG_ENOTSUP;
+  if (joint ? a->bias != nullptr : (a->Skv % KT != 0 || a->q_prescaled)) return MRAG_ENOTSUP;
+  const int skvp = pad_keys(a->Skv);                         // == Skv on the old entry point
+  const bool ragged = skvp != a->Skv;
   if (((uintptr_t)a->Q | (uintptr_t)a->K | (uintptr_t)a->V | (uintptr_t)a->workspace) & 15) return MRAG_EINVAL;
   if ((a->q_sb | a->q_ss | a->q_sh | a->k_sb | a->k_ss | a->k_sh | a->v_sb | a->v_ss | a->v_sh) % 8 != 0) return MRAG_EINVAL;
   if (((uintptr_t)a->O & 7) || (a->o_sb | a->o_ss) % 4 != 0 || (a->resid && ((uintptr_t)a->resid & 7))) return MRAG_EINVAL;
-  if (a->workspace_bytes < mrag_attn_fp8_workspace_bytes(a->B, a->H, a->Sq, a->Skv)) return MRAG_EINVAL;
+  if (a->workspace_bytes < mrag_attn_fp8_workspace_bytes(a->B, a->H, a->Sq, skvp)) return MRAG_EINVAL;
   Fp8P fp{};
   AttnP& p = fp.a;
   p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.V = (const bf16_t*)a->V;
@@ -319,28 +370,44 @@ extern "C" int mrag_attn_fwd_fp8(void* stream, const mrag_attn_args* a) {
   p.v_sb = a->v_sb; p.v_ss = a->v_ss; p.v_sh = a->v_sh;
   p.o_sb = a->o_sb; p.o_ss = a->o_ss;
   p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Skv = a->Skv; p.kv_div = 1;
-  p.qscale = a->scale * 1.4426950408889634f;
+  // q_prescaled: Q already carries scale * log2 e (the QKV GEMM's q_premul) -- the quantiser's multiplier and the exponent y both use 1
+  p.qscale = a->q_prescaled ? 1.0f : a->scale * 1.4426950408889634f;
   p.out_scale = a->out_scale;
   p.n_qtiles = (a->Sq + 255) / 256;
   const size_t bh = (size_t)a->B * a->H;
   char* ws = (char*)a->workspace;
   fp.amax = (unsigned*)ws; ws += align256(bh * 16);
   fp.q8 = (uint8_t*)ws; ws += align256(bh * a->Sq * 64);
-  fp.k8 = (uint8_t*)ws; ws += align256(bh * a->Skv * 64);
+  fp.k8 = (uint8_t*)ws; ws += align256(bh * skvp * 64);
   fp.v8 = (uint8_t*)ws;
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(fp.amax, 0, bh * 16, s);
   if (e != hipSuccess) return (int)e;
-  const int smax = a->Sq > a->Skv ? a->Sq : a->Skv;
+  const int smax = a->Sq > skvp ? a->Sq : skvp;               // quant_kernel's tile grid covers the padding keys too
   int chunks = (smax + 31) / 32;
   if (chunks > 64) chunks = 64;
   MRAG_LAUNCH(amax_kernel, dim3(chunks, (unsigned)bh, 3), dim3(256), 0, s, p, fp.amax);
   MRAG_LAUNCH_CHECK();
-  MRAG_LAUNCH(quant_kernel, dim3((smax + 63) / 64, (unsigned)bh, 3), dim3(256), 0, s, fp);
+  // whole stages (Skv % 128 == 0) launch the instantiations the UNets run, whichever entry point was called
+  if (ragged) MRAG_LAUNCH(quant_kernel<true>, dim3((smax + 63) / 64, (unsigned)bh, 3), dim3(256), 0, s, fp);
+  else MRAG_LAUNCH(quant_kernel<false>, dim3((smax + 63) / 64, (unsigned)bh, 3), dim3(256), 0, s, fp);
   MRAG_LAUNCH_CHECK();
+  if (joint && (a->tuning & MRAG_ATTN_TUNE_FP8_QUANT_ONLY)) return MRAG_OK;   // developer knob: the quantisers' share of a call (tools/attn_fp8_joint_measure.py)
   const size_t lds = NS8 * STAGE;
-  const int rc = launch_dyn_lds(attn8_kernel, dim3(p.n_qtiles * (unsigned)bh), dim3(512), lds, s, fp);
+  const int rc = ragged ? launch_dyn_lds(attn8_kernel<true>, dim3(p.n_qtiles * (unsigned)bh), dim3(512), lds, s, fp)
+                        : launch_dyn_lds(attn8_kernel<false>, dim3(p.n_qtiles * (unsigned)bh), dim3(512), lds, s, fp);
   if (rc != MRAG_OK) return rc;
   MRAG_COUNT(MRAG_K_ATTN_FP8);
   return MRAG_OK;
 }
+
+}  // namespace
+
+extern "C" int mrag_attn_fwd_fp8(void* stream, const mrag_attn_args* a) { return fwd_fp8(stream, a, false); }
+
+extern "C" int64_t mrag_attn_joint_fp8_workspace_bytes(int32_t B, int32_t H, int32_t Sq, int32_t Skv) {
+  if (Skv <= 0) return 0;
+  return mrag_attn_fp8_workspace_bytes(B, H, Sq, pad_keys(Skv));
+}
+
+extern "C" int mrag_attn_joint_fwd_fp8(void* stream, const mrag_attn_args* a) { return fwd_fp8(stream, a, true); }

@@ -23,6 +23,7 @@ LOG2E = 1.4426950408889634
 TUNING = {"gemm": 0, "attn": 0, "attn_no_split": False, "no_qkv_fuse": False, "no_batched_w": False, "gn_fold": False}
 GEMM_TUNE_NO_WIDE, GEMM_TUNE_NO_STAGED, GEMM_TUNE_GEGLU_NO_STAGED = 1, 2, 4
 ATTN_TUNE_NO_TINY, ATTN_TUNE_LEGACY = 1, 8
+ATTN_TUNE_FP8_QUANT_ONLY = 16   # mrag_attn_joint_fwd_fp8 stops after amax + quantise (tools/attn_fp8_joint_measure.py)
 
 
 class HipOnly(RuntimeError):
@@ -239,16 +240,13 @@ def fp8_attention_supported(Sq: int, Skv: int, kv_batch_div: int = 1, mask=None,
     return mask is None and kv_batch_div == 1 and not q_prescaled and Skv % 128 == 0 and Skv >= 512 and Sq > 128
 
 
-def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, out: Optional[torch.Tensor] = None,
-              resid: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, kv_batch_div: int = 1,
-              scale: Optional[float] = None, out_scale: float = 1.0, q_prescaled: bool = False, fp8: bool = False,
-              bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """softmax(q k^T * scale [masked]) v for head_dim 64.  fp8=True: the e4m3 MFMA path (mrag_attn_fwd_fp8; raises on shapes it does not take).
+def fp8_joint_attention_supported(Sq: int, Skv: int, kv_batch_div: int = 1, mask=None) -> bool:
+    """shapes mrag_attn_joint_fwd_fp8 takes (include/mrag_hip.h): any row and key count from 512 keys up, pre-scaled Q or not"""
+    return mask is None and kv_batch_div == 1 and Skv >= 512 and Sq >= 1
 
-    q [B, Sq, H, 64], k/v [Bkv, Skv, H, 64] (any strides with the last dim contiguous, e.g. views of a
-    fused QKV buffer); out/resid [B, Sq, H*64] with the last two dims packed.  mask: bool/uint8
-    [Sq, Skv], True = blocked.  out = resid + out_scale * attention when resid is given.
-    """
+
+def _attention_args(q, k, v, out, resid, mask, kv_batch_div, scale, out_scale, q_prescaled, bias, fp8=False):
+    """the checks and the mrag_attn_args block every attention entry point shares -> (args, out, mask as the kernels read it); `fp8`: a path that takes no bias"""
     for n, t in (("q", q), ("k", k), ("v", v)):
         _dev(t, name=n)
         if t.dim() != 4 or t.shape[-1] != 64 or t.stride(-1) != 1:
@@ -292,20 +290,39 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, out: Optiona
     a.out_scale = out_scale
     a.q_prescaled = 1 if q_prescaled else 0
     a.tuning = TUNING["attn"]
+    return a, out, mask
+
+
+def _fp8_attention_launch(a: AttnArgs, device, need: int, entry: str, label: str) -> None:
+    """one of the two fp8 entry points on the "fp8" workspace (grow-only, per device and stream: no host synchronisation, graph-capturable once grown)"""
+    ws = _attn_workspace(device, need, "fp8")
+    a.workspace, a.workspace_bytes = _p(ws), ws.numel()
+    timed = KERNEL_TIMING is not None and a.Skv >= 1024
+    if timed:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    check(getattr(_lib.lib(), entry)(_stream(), ctypes.byref(a)), entry)
+    if timed:
+        e1.record()
+        KERNEL_TIMING.append((label, 4.0 * a.B * a.H * a.Sq * a.Skv * 64, e0, e1))
+
+
+def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, out: Optional[torch.Tensor] = None,
+              resid: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, kv_batch_div: int = 1,
+              scale: Optional[float] = None, out_scale: float = 1.0, q_prescaled: bool = False, fp8: bool = False,
+              bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax(q k^T * scale [masked]) v for head_dim 64.  fp8=True: the e4m3 MFMA path (mrag_attn_fwd_fp8; raises on shapes it does not take).
+
+    q [B, Sq, H, 64], k/v [Bkv, Skv, H, 64] (any strides with the last dim contiguous, e.g. views of a
+    fused QKV buffer); out/resid [B, Sq, H*64] with the last two dims packed.  mask: bool/uint8
+    [Sq, Skv], True = blocked.  out = resid + out_scale * attention when resid is given.
+    """
+    a, out, mask = _attention_args(q, k, v, out, resid, mask, kv_batch_div, scale, out_scale, q_prescaled, bias, fp8)
+    B, H, Sq, Skv = a.B, a.H, a.Sq, a.Skv
     if fp8:
         if not fp8_attention_supported(Sq, Skv, kv_batch_div, mask, q_prescaled):
             raise ValueError(f"fp8 attention does not take Sq={Sq} Skv={Skv} kv_batch_div={kv_batch_div} (see fp8_attention_supported)")
-        need = _lib.lib().mrag_attn_fp8_workspace_bytes(B, H, Sq, Skv)
-        ws = _attn_workspace(q.device, need, "fp8")
-        a.workspace, a.workspace_bytes = _p(ws), ws.numel()
-        timed = KERNEL_TIMING is not None and Skv >= 1024
-        if timed:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        check(_lib.lib().mrag_attn_fwd_fp8(_stream(), ctypes.byref(a)), "mrag_attn_fwd_fp8")
-        if timed:
-            e1.record()
-            KERNEL_TIMING.append(("attn_fwd_fp8", 4.0 * B * H * Sq * Skv * 64, e0, e1))
+        _fp8_attention_launch(a, q.device, _lib.lib().mrag_attn_fp8_workspace_bytes(B, H, Sq, Skv), "mrag_attn_fwd_fp8", "attn_fwd_fp8")
         return out
     if mask is None and not TUNING["attn_no_split"]:
         need = _lib.lib().mrag_attn_workspace_bytes(B, H, Sq, Skv)   # > 0: long sequence with a ragged last query tile (key-split tail)
@@ -320,6 +337,18 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, out: Optiona
     if timed:
         e1.record()
         KERNEL_TIMING.append(("attn_fwd", 4.0 * B * H * Sq * Skv * 64, e0, e1))
+    return out
+
+
+def joint_attention_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, out: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
+                        scale: Optional[float] = None, out_scale: float = 1.0, q_prescaled: bool = False) -> torch.Tensor:
+    """`attention` on the e4m3 MFMA path for the CogVideoX DiT's joint [text ; video] sequence (mrag_attn_joint_fwd_fp8): any key count >= 512 -- the ragged
+    last 128-key stage is zero-padded and masked inside -- and a Q that already carries scale * log2 e (q_prescaled).  Layouts and checks are `attention`'s;
+    raises ValueError on the shapes the entry point does not take (`fp8_joint_attention_supported`): opting in is explicit, so is its refusal."""
+    a, out, _ = _attention_args(q, k, v, out, resid, None, 1, scale, out_scale, q_prescaled, None, True)
+    if not fp8_joint_attention_supported(a.Sq, a.Skv):
+        raise ValueError(f"fp8 joint attention does not take Sq={a.Sq} Skv={a.Skv} (see fp8_joint_attention_supported)")
+    _fp8_attention_launch(a, q.device, _lib.lib().mrag_attn_joint_fp8_workspace_bytes(a.B, a.H, a.Sq, a.Skv), "mrag_attn_joint_fwd_fp8", "attn_joint_fwd_fp8")
     return out
 
 
