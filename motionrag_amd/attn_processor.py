@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .layers import WeightCache
 
 
 def packed_score_layout(heads: int, keys: int):
@@ -70,35 +71,11 @@ class Attention(nn.Module):
         return self.processor(self, hidden_states, encoder_hidden_states=encoder_hidden_states, **kwargs)
 
 
-def _wkey(t: torch.Tensor):
-    """cache key of a weight tensor: storage address + in-place version (load_state_dict copies in place)"""
-    return (t.data_ptr(), t._version)
-
-
 def _cat_weights(mods, attr="weight"):
     ts = [getattr(m, attr) for m in mods]
     if any(t is None for t in ts):
         return None
     return torch.cat([t.detach() for t in ts], dim=0).contiguous()
-
-
-class _FusedWeights:
-    """per-`Attention` cache of concatenated projection weights (built once, memory plumbing only).  One slot per KIND of fused operand (the first element of
-    a tuple key): a key whose weight addresses / versions changed REPLACES the slot, so updated weights do not leave stale copies behind."""
-
-    def __init__(self):
-        self._cache = {}
-
-    def get(self, key, builder):
-        kind = key[0] if isinstance(key, tuple) else key
-        ent = self._cache.get(kind)
-        if ent is None or ent[0] != key:
-            ent = (key, builder())
-            self._cache[kind] = ent
-        return ent[1]
-
-    def clear(self):
-        self._cache.clear()
 
 
 def _joint_sdpa(q, k, v, fp8_attn: bool):
@@ -122,18 +99,14 @@ def joint_attention_core(attn, proc, x: torch.Tensor, text_len: int, rope, ip_hi
     B, S, D = x.shape
     H = attn.heads
     fw = proc._fused
-    wqkv, bqkv = fw.get(("qkv", _wkey(attn.to_q.weight), _wkey(attn.to_k.weight), _wkey(attn.to_v.weight)), lambda: (_cat_weights([attn.to_q, attn.to_k, attn.to_v]),
-                                                      _cat_weights([attn.to_q, attn.to_k, attn.to_v], "bias")))
+    qkv_lins = (attn.to_q, attn.to_k, attn.to_v)
+    wqkv, bqkv = fw.get("qkv", tuple(m.weight for m in qkv_lins) + tuple(m.bias for m in qkv_lins),
+                        lambda: (_cat_weights(qkv_lins), _cat_weights(qkv_lins, "bias")))
     cos = sin = None
     if rope is not None:
-        # single slot, valid only for the SAME table objects (the entry holds references, so their addresses cannot be recycled under it): a
-        # pipeline that rebuilds image_rotary_emb per call replaces the entry instead of growing the cache
-        ent = fw._cache.get("rope")
-        if ent is None or ent[0] is not rope[0] or ent[1] is not rope[1] or ent[2] != (S, text_len, rope[0]._version, rope[1]._version):
-            ent = (rope[0], rope[1], (S, text_len, rope[0]._version, rope[1]._version),
-                   rope[0].to(device=x.device, dtype=torch.float32).contiguous(), rope[1].to(device=x.device, dtype=torch.float32).contiguous())
-            fw._cache["rope"] = ent
-        cos, sin = ent[3], ent[4]
+        # single slot, valid only for the SAME table objects: a pipeline that rebuilds image_rotary_emb per call replaces the entry instead
+        # of growing the cache
+        cos, sin = fw.get("rope", (rope[0], rope[1]), lambda: tuple(t.to(device=x.device, dtype=torch.float32).contiguous() for t in rope[:2]))
         if getattr(attn, "is_cross_attention", False):
             raise NotImplementedError("RoPE on Q only (is_cross_attention=True) is not used by CogVideoX attn1")
     nq, nk = getattr(attn, "norm_q", None), getattr(attn, "norm_k", None)
@@ -143,7 +116,7 @@ def joint_attention_core(attn, proc, x: torch.Tensor, text_len: int, rope, ip_hi
     if fp8_qkv:
         # the concatenated weight quantised once per output channel; the projection with a plain epilogue, then norm_q / norm_k + RoPE in place
         # (the two-kernel form ops.qkv_linear_qknorm_rope falls back to)
-        w8, w_exp = fw.get(("qkv8", _wkey(attn.to_q.weight), _wkey(attn.to_k.weight), _wkey(attn.to_v.weight)), lambda: ops.quant_rows_e4m3(wqkv))
+        w8, w_exp = fw.get("qkv8", tuple(m.weight for m in qkv_lins), lambda: ops.quant_rows_e4m3(wqkv))
         qkv = ops.linear_fp8(x, w8, w_exp, bqkv)
         ops.qknorm_rope_(qkv, H, nq.weight if nq is not None else None, nq.bias if nq is not None else None, nk.weight if nk is not None else None,
                          nk.bias if nk is not None else None, cos, sin, text_len, eps=nq.eps if nq is not None else 1e-6, q_premul=ops.LOG2E * 64 ** -0.5)
@@ -189,7 +162,7 @@ def _motion_branch(attn, proc, o, ip_hidden_states, scale):
         ip = ip_hidden_states if ip_hidden_states.dtype == torch.bfloat16 else ip_hidden_states.to(torch.bfloat16)
         ip = ip.contiguous()
         r = B // ip.size(0)                                                       # :254
-        wkv = fw.get(("ipkv", _wkey(proc.to_k_ip[0].weight), _wkey(proc.to_v_ip[0].weight)), lambda: _cat_weights([proc.to_k_ip[0], proc.to_v_ip[0]]))
+        wkv = fw.get("ipkv", (proc.to_k_ip[0].weight, proc.to_v_ip[0].weight), lambda: _cat_weights([proc.to_k_ip[0], proc.to_v_ip[0]]))
         if FOLD_IP_QUERY and ip.size(1) <= 32:
             # The motion tokens are fixed for a clip, so to_q_ip is folded into the keys ONCE per clip:
             #   to_q_ip(o)_h . K_h^T = o . (K_h . Wq_h)^T = o . M_h^T,  M [B', NW, D]: head h's nk keys in rows KS h .. KS h + nk - 1
@@ -216,16 +189,12 @@ def _motion_branch(attn, proc, o, ip_hidden_states, scale):
                 M = torch.empty(Bp, NW, D, dtype=torch.bfloat16, device=ip.device)
                 for bp in range(Bp):
                     ops.linear(A[bp].view(NW, D), wq_t, out=M[bp])
-                return M, kv0[..., D:], KS
-            # cache hit only for the SAME tensor object at the same version: the entry keeps a reference to `ip`, so its address cannot be
-            # recycled for another clip's tokens while the entry lives (a data_ptr key alone would go stale silently)
-            ent = fw._cache.get("ipfold")
-            if ent is None or ent[0] is not ip or ent[1] != ip._version or ent[2] != (_wkey(proc.to_q_ip[0].weight), _wkey(proc.to_k_ip[0].weight), _wkey(proc.to_v_ip[0].weight)) or ent[5] != KS:
-                ent = (ip, ip._version, (_wkey(proc.to_q_ip[0].weight), _wkey(proc.to_k_ip[0].weight), _wkey(proc.to_v_ip[0].weight))) + build()
-                fw._cache["ipfold"] = ent
-            M, v_ip = ent[3], ent[4]
+                return M, kv0[..., D:]
+            # cache hit only for the SAME `ip` object at the same version (a data_ptr key alone would go stale silently when the address is
+            # recycled for another clip's tokens); the caller keeps `ip` alive to pass it again, and the entry goes when `ip` does
+            M, v_ip = fw.get(("ipfold", KS), (ip, proc.to_q_ip[0].weight, proc.to_k_ip[0].weight, proc.to_v_ip[0].weight), build)
             sc = ops.linear_per_sample(o, M, samples_per_weight=r)                # [B, S, NW]
-            ops.ip_attn_folded_(sc, v_ip, o, H, ip.size(1), kv_batch_div=r, scale=0.125, out_scale=float(scale), key_stride=ent[5])
+            ops.ip_attn_folded_(sc, v_ip, o, H, ip.size(1), kv_batch_div=r, scale=0.125, out_scale=float(scale), key_stride=KS)
         else:
             ip_q = ops.linear(o, proc.to_q_ip[0].weight)                          # :250  (text tokens included)
             kv = ops.linear(ip, wkv)                                              # :251-252 (one GEMM)
@@ -253,7 +222,7 @@ class APAdapterCogVideoXAttnProcessor2_0(nn.Module):
         self.to_k_ip = nn.ModuleList([nn.Linear(cross_attention_dim, hidden_size, bias=False) for _ in num_tokens])
         self.to_v_ip = nn.ModuleList([nn.Linear(cross_attention_dim, hidden_size, bias=False) for _ in num_tokens])
         self.to_q_ip = nn.ModuleList([nn.Linear(hidden_size, hidden_size, bias=False) for _ in num_tokens])
-        self._fused = _FusedWeights()
+        self._fused = WeightCache()
 
     def _unpack(self, image_rotary_emb, action_hidden_states):
         if isinstance(image_rotary_emb, tuple) and isinstance(image_rotary_emb[1], torch.Tensor) and isinstance(image_rotary_emb[0], tuple):
@@ -293,7 +262,7 @@ class APAdapterAttnProcessor2_0(nn.Module):
         self.to_k_ip = nn.ModuleList([nn.Linear(cross_attention_dim, hidden_size, bias=False) for _ in num_tokens])
         self.to_v_ip = nn.ModuleList([nn.Linear(cross_attention_dim, hidden_size, bias=False) for _ in num_tokens])
         self.to_q_ip = nn.ModuleList([nn.Linear(hidden_size, hidden_size, bias=False) for _ in num_tokens])
-        self._fused = _FusedWeights()
+        self._fused = WeightCache()
 
     def __call__(self, attn, hidden_states: torch.Tensor, encoder_hidden_states=None, action_hidden_states=None,
                  attention_mask=None, temb=None, scale: float = 1.0, ip_adapter_masks=None, block_residual: Optional[torch.Tensor] = None):
@@ -321,14 +290,15 @@ class APAdapterAttnProcessor2_0(nn.Module):
             raise NotImplementedError("head_dim 64 only")
         q = ops.linear(hidden_states, attn.to_q.weight, attn.to_q.bias)            # :65
         enc = hidden_states if encoder_hidden_states is None else encoder_hidden_states.contiguous()
-        wkv, bkv = self._fused.get(("kv", _wkey(attn.to_k.weight), _wkey(attn.to_v.weight)), lambda: (_cat_weights([attn.to_k, attn.to_v]), _cat_weights([attn.to_k, attn.to_v], "bias")))
+        wkv, bkv = self._fused.get("kv", (attn.to_k.weight, attn.to_v.weight, attn.to_k.bias, attn.to_v.bias),
+                                   lambda: (_cat_weights([attn.to_k, attn.to_v]), _cat_weights([attn.to_k, attn.to_v], "bias")))
         kv = ops.linear(enc, wkv, bkv)                                             # :72-73
         o = ops.attention(q.view(B, L, H, 64), kv[..., :C].unflatten(-1, (H, 64)), kv[..., C:].unflatten(-1, (H, 64)))   # :85-90
         if ip_hidden_states is not None and self.scale[0] != 0:                    # :93-139
             ip = ip_hidden_states.to(torch.bfloat16).contiguous()
             r = B // ip.size(0)
             ip_q = ops.linear(o, self.to_q_ip[0].weight)
-            wip = self._fused.get(("ipkv", _wkey(self.to_k_ip[0].weight), _wkey(self.to_v_ip[0].weight)), lambda: _cat_weights([self.to_k_ip[0], self.to_v_ip[0]]))
+            wip = self._fused.get("ipkv", (self.to_k_ip[0].weight, self.to_v_ip[0].weight), lambda: _cat_weights([self.to_k_ip[0], self.to_v_ip[0]]))
             ipkv = ops.linear(ip, wip)
             ops.attention(ip_q.view(B, L, H, 64), ipkv[..., :C].unflatten(-1, (H, 64)), ipkv[..., C:].unflatten(-1, (H, 64)),
                           out=o, resid=o, kv_batch_div=r, out_scale=float(self.scale[0]))

@@ -14,27 +14,18 @@ import torch
 from torch import nn
 
 from . import ops
-from .dynamicrafter import _CACHE
 from .encoders import assemble_tokens, pixels_to_patch_rows
-
-
-def _b(t: torch.Tensor) -> torch.Tensor:
-    t = t.detach()
-    return t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)
-
-
-class _H(nn.Module):
-    pass
+from .layers import CACHE, Holder, bf16, prenorm_block
 
 
 class _Layer(nn.Module):
     def __init__(self, d: int, ff: int, eps: float):
         super().__init__()
-        self.self_attn = _H()
+        self.self_attn = Holder()
         for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
             setattr(self.self_attn, n, nn.Linear(d, d))
         self.layer_norm1 = nn.LayerNorm(d, eps=eps)
-        self.mlp = _H()
+        self.mlp = Holder()
         self.mlp.fc1, self.mlp.fc2 = nn.Linear(d, ff), nn.Linear(ff, d)
         self.layer_norm2 = nn.LayerNorm(d, eps=eps)
 
@@ -57,13 +48,13 @@ class CLIPVisionModelWithProjection(nn.Module):
             raise NotImplementedError(f"head_dim {self.head_dim}: no attention kernel")
         self.hidden_size, self.heads, self.patch_size, self.eps, self.image_size = hidden_size, num_attention_heads, patch_size, layer_norm_eps, image_size
         n_pos = (image_size // patch_size) ** 2 + 1
-        vm = self.vision_model = _H()
-        vm.embeddings = _H()
+        vm = self.vision_model = Holder()
+        vm.embeddings = Holder()
         vm.embeddings.class_embedding = nn.Parameter(torch.randn(hidden_size))
         vm.embeddings.patch_embedding = nn.Conv2d(num_channels, hidden_size, patch_size, stride=patch_size, bias=False)
         vm.embeddings.position_embedding = nn.Embedding(n_pos, hidden_size)
         vm.pre_layrnorm = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
-        vm.encoder = _H()
+        vm.encoder = Holder()
         vm.encoder.layers = nn.ModuleList(_Layer(hidden_size, intermediate_size, layer_norm_eps) for _ in range(num_hidden_layers))
         vm.post_layernorm = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
         self.visual_projection = nn.Linear(hidden_size, projection_dim, bias=False)
@@ -75,8 +66,8 @@ class CLIPVisionModelWithProjection(nn.Module):
         layers = self._layers()
         x = _tower(pixel_values, vm.embeddings.patch_embedding, vm.embeddings.class_embedding, vm.embeddings.position_embedding.weight, vm.pre_layrnorm, layers,
                    self.heads, self.head_dim, self.patch_size, self.eps, id(self))
-        pooled = ops.layernorm(x[:, 0].contiguous(), _b(vm.post_layernorm.weight), _b(vm.post_layernorm.bias), self.eps)
-        return CLIPVisionOutput(ops.linear(pooled, _b(self.visual_projection.weight)), x)
+        pooled = ops.layernorm(x[:, 0].contiguous(), bf16(vm.post_layernorm.weight), bf16(vm.post_layernorm.bias), self.eps)
+        return CLIPVisionOutput(ops.linear(pooled, bf16(self.visual_projection.weight)), x)
 
 
     MEAN, STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
@@ -85,9 +76,9 @@ class CLIPVisionModelWithProjection(nn.Module):
         out = []
         for L in self.vision_model.encoder.layers:
             sa = L.self_attn
-            w, b = _CACHE.get(("clip_qkv", id(sa)), (sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight, sa.q_proj.bias, sa.k_proj.bias, sa.v_proj.bias),
-                              lambda: (torch.cat([_b(sa.q_proj.weight), _b(sa.k_proj.weight), _b(sa.v_proj.weight)], 0).contiguous(),
-                                       torch.cat([_b(sa.q_proj.bias), _b(sa.k_proj.bias), _b(sa.v_proj.bias)], 0).contiguous()))
+            w, b = CACHE.get(("clip_qkv", id(sa)), (sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight, sa.q_proj.bias, sa.k_proj.bias, sa.v_proj.bias),
+                              lambda: (torch.cat([bf16(sa.q_proj.weight), bf16(sa.k_proj.weight), bf16(sa.v_proj.weight)], 0).contiguous(),
+                                       torch.cat([bf16(sa.q_proj.bias), bf16(sa.k_proj.bias), bf16(sa.v_proj.bias)], 0).contiguous()))
             out.append((L.layer_norm1, w, b, sa.out_proj, L.layer_norm2, L.mlp.fc1, L.mlp.fc2))
         return out
 
@@ -106,8 +97,8 @@ class CLIPVisionModelWithProjection(nn.Module):
                                     mean=self.MEAN, std=self.STD)
         x = _tower_from_rows(rows, B, size // self.patch_size, vm.embeddings.patch_embedding, vm.embeddings.class_embedding, vm.embeddings.position_embedding.weight,
                              vm.pre_layrnorm, self._layers(), self.heads, self.head_dim, self.eps, id(self))
-        pooled = ops.layernorm(x[:, 0].contiguous(), _b(vm.post_layernorm.weight), _b(vm.post_layernorm.bias), self.eps)
-        return CLIPVisionOutput(ops.linear(pooled, _b(self.visual_projection.weight)), x)
+        pooled = ops.layernorm(x[:, 0].contiguous(), bf16(vm.post_layernorm.weight), bf16(vm.post_layernorm.bias), self.eps)
+        return CLIPVisionOutput(ops.linear(pooled, bf16(self.visual_projection.weight)), x)
 
 
 def _tower(pixel_values, conv, class_embedding, positional, ln_pre, layers, heads, head_dim, ps, eps, owner_id) -> torch.Tensor:
@@ -127,24 +118,14 @@ def _tower_from_rows(rows, B, grid, conv, class_embedding, positional, ln_pre, l
     D = conv.weight.shape[0]
 
     def build():
-        w = _b(conv.weight).reshape(D, -1)
+        w = bf16(conv.weight).reshape(D, -1)
         return torch.nn.functional.pad(w, (0, rows.shape[1] - w.shape[1])).contiguous()
-    x = ops.linear(rows, _CACHE.get(("clip_patch", id(conv), rows.shape[1]), conv.weight, build), _b(conv.bias) if conv.bias is not None else None).view(B, grid * grid, D)
-    cls = _CACHE.get(("clip_cls", owner_id), class_embedding, lambda: _b(class_embedding).reshape(1, D).contiguous())
-    x = assemble_tokens(x, cls, _b(positional).contiguous())
-    x = ops.layernorm(x, _b(ln_pre.weight), _b(ln_pre.bias), eps)
-    S = x.shape[1]
+    x = ops.linear(rows, CACHE.get(("clip_patch", id(conv), rows.shape[1]), conv.weight, build), bf16(conv.bias)).view(B, grid * grid, D)
+    cls = CACHE.get(("clip_cls", owner_id), class_embedding, lambda: bf16(class_embedding).reshape(1, D).contiguous())
+    x = assemble_tokens(x, cls, bf16(positional).contiguous())
+    x = ops.layernorm(x, bf16(ln_pre.weight), bf16(ln_pre.bias), eps)
     for ln1, w, b, out_proj, ln2, fc1, fc2 in layers:
-        h = ops.layernorm(x, _b(ln1.weight), _b(ln1.bias), eps)
-        qkv = ops.linear(h, w, b).view(B, S, 3, heads, head_dim)
-        if head_dim == 64:
-            a = ops.attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2])
-        else:
-            a = ops.attention_small(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2])
-        x = ops.linear(a, _b(out_proj.weight), _b(out_proj.bias), epilogue=ops.EPI_RESID, resid=x)
-        h = ops.layernorm(x, _b(ln2.weight), _b(ln2.bias), eps)
-        h = ops.linear(h, _b(fc1.weight), _b(fc1.bias), epilogue=ops.EPI_GELU_ERF)
-        x = ops.linear(h, _b(fc2.weight), _b(fc2.bias), epilogue=ops.EPI_RESID, resid=x)
+        x = prenorm_block(x, heads, ln1, w, b, out_proj, ln2, fc1, fc2, eps=eps, head_dim=head_dim)
     return x
 
 
@@ -153,12 +134,12 @@ class _OCBlock(nn.Module):
     def __init__(self, d: int, ff: int):
         super().__init__()
         self.ln_1 = nn.LayerNorm(d)
-        self.attn = _H()
+        self.attn = Holder()
         self.attn.in_proj_weight = nn.Parameter(torch.randn(3 * d, d) * d ** -0.5)
         self.attn.in_proj_bias = nn.Parameter(torch.zeros(3 * d))
         self.attn.out_proj = nn.Linear(d, d)
         self.ln_2 = nn.LayerNorm(d)
-        self.mlp = _H()
+        self.mlp = Holder()
         self.mlp.c_fc, self.mlp.c_proj = nn.Linear(d, ff), nn.Linear(ff, d)
 
 
@@ -177,7 +158,7 @@ class OpenCLIPVisual(nn.Module):
         self.class_embedding = nn.Parameter(torch.randn(width) * width ** -0.5)
         self.positional_embedding = nn.Parameter(torch.randn((image_size // patch_size) ** 2 + 1, width) * width ** -0.5)
         self.ln_pre = nn.LayerNorm(width)
-        self.transformer = _H()
+        self.transformer = Holder()
         self.transformer.resblocks = nn.ModuleList(_OCBlock(width, int(width * mlp_ratio)) for _ in range(layers))
         self.ln_post = nn.LayerNorm(width)
         self.proj = nn.Parameter(torch.randn(width, output_dim) * width ** -0.5)
@@ -185,7 +166,7 @@ class OpenCLIPVisual(nn.Module):
     @torch.no_grad()
     def tokens(self, pixel_values: torch.Tensor) -> torch.Tensor:
         """every token after the last block, before `ln_post` -- what `encode_with_vision_transformer` returns (condition.py:348-380)"""
-        layers = [(r.ln_1, _b(r.attn.in_proj_weight), _b(r.attn.in_proj_bias), r.attn.out_proj, r.ln_2, r.mlp.c_fc, r.mlp.c_proj) for r in self.transformer.resblocks]
+        layers = [(r.ln_1, bf16(r.attn.in_proj_weight), bf16(r.attn.in_proj_bias), r.attn.out_proj, r.ln_2, r.mlp.c_fc, r.mlp.c_proj) for r in self.transformer.resblocks]
         return _tower(pixel_values, self.conv1, self.class_embedding, self.positional_embedding, self.ln_pre, layers, self.heads, self.head_dim, self.patch_size_,
                       self.ln_pre.eps, id(self))
 
@@ -201,7 +182,7 @@ class FrozenOpenCLIPImageEmbedderV2(nn.Module):
 
     def __init__(self, model=None, preprocess=None, freeze: bool = True, layer: str = "pooled", antialias: bool = True, **config):
         super().__init__()
-        self.model = _H()
+        self.model = Holder()
         self.model.visual = model if isinstance(model, nn.Module) else OpenCLIPVisual(**config)
         self.preprocess_fn, self.layer, self.antialias = preprocess, layer, antialias
         if freeze:
@@ -223,5 +204,5 @@ class FrozenOpenCLIPImageEmbedderV2(nn.Module):
         rows = pixels_to_patch_rows(x[:, None], resize=224, crop=224, mode="kornia-bicubic" if self.antialias else "kornia-bicubic-noaa",
                                     patch=(1, v.patch_size_, v.patch_size_), mean=self.MEAN, std=self.STD)
         # rows are already the patch-GEMM operand: run the tower from them (same code path as `tokens`, minus the identity pixel pass)
-        layers = [(r.ln_1, _b(r.attn.in_proj_weight), _b(r.attn.in_proj_bias), r.attn.out_proj, r.ln_2, r.mlp.c_fc, r.mlp.c_proj) for r in v.transformer.resblocks]
+        layers = [(r.ln_1, bf16(r.attn.in_proj_weight), bf16(r.attn.in_proj_bias), r.attn.out_proj, r.ln_2, r.mlp.c_fc, r.mlp.c_proj) for r in v.transformer.resblocks]
         return _tower_from_rows(rows, B, 224 // v.patch_size_, v.conv1, v.class_embedding, v.positional_embedding, v.ln_pre, layers, v.heads, v.head_dim, v.ln_pre.eps, id(v))

@@ -28,7 +28,8 @@ import torch
 from torch import nn
 
 from . import ops
-from .attn_processor import APAdapterCogVideoXAttnProcessor2_0, Attention, _wkey, joint_attention_core
+from .attn_processor import APAdapterCogVideoXAttnProcessor2_0, Attention, joint_attention_core
+from .layers import WeightCache, cat0
 
 
 class _LayerNormZero(nn.Module):
@@ -89,8 +90,7 @@ class _PlainProcessor:
     """blocks without a motion adapter: same fused path, adapter branch skipped"""
 
     def __init__(self):
-        from .attn_processor import _FusedWeights
-        self._fused = _FusedWeights()
+        self._fused = WeightCache()
         self.scale = [0.0]
 
 
@@ -150,10 +150,9 @@ class CogVideoXTransformer3DModel(nn.Module):
         self.norm_final = nn.LayerNorm(D, eps=norm_eps)
         self.norm_out = _AdaLayerNorm(time_embed_dim, D, norm_eps)
         self.proj_out = nn.Linear(D, patch_size * patch_size * out_channels)
-        self._fused: Dict[str, torch.Tensor] = {}
+        # "mod" / "patch_w" (below) and (site, layer) -> the weight's e4m3 rows + exponents (set_linear_precision)
+        self._fused = WeightCache()
         self._plain = _PlainProcessor()
-        from .attn_processor import _FusedWeights
-        self._fp8_weights = _FusedWeights()                        # (site, layer) -> the weight's e4m3 rows + exponents (set_linear_precision)
 
     # ---- diffusers-style processor plumbing (cogvideox/module.py:163-175 uses exactly these two) ----
     @property
@@ -173,19 +172,15 @@ class CogVideoXTransformer3DModel(nn.Module):
 
     # ---- fused weights (built once) ----
     def _mod_weights(self):
-        tag = tuple((w.data_ptr(), w.dtype, w._version) for w in (self.norm_out.linear.weight, self.transformer_blocks[0].norm1.linear.weight,
-                                                                    self.patch_embed.proj.weight))
-        if self._fused.get("tag") != tag:
-            self._fused = {"tag": tag}
-            ws, bs = [], []
-            for blk in self.transformer_blocks:
-                for n in (blk.norm1, blk.norm2):
-                    ws.append(n.linear.weight.detach()); bs.append(n.linear.bias.detach())
-            ws.append(self.norm_out.linear.weight.detach()); bs.append(self.norm_out.linear.bias.detach())
-            self._fused["mod_w"] = torch.cat(ws, 0).contiguous()
-            self._fused["mod_b"] = torch.cat(bs, 0).contiguous()
-            self._fused["patch_w"] = self.patch_embed.proj.weight.detach().reshape(self.cfg["dim"], -1).contiguous()
-        return self._fused["mod_w"], self._fused["mod_b"]
+        """every block's AdaLN-zero modulation linear and norm_out's, row-concatenated: one GEMM per step.  Looked up once per step, so ALL of
+        the weights and biases are checked, not a sample of them"""
+        lins = [n.linear for blk in self.transformer_blocks for n in (blk.norm1, blk.norm2)] + [self.norm_out.linear]
+        return self._fused.get("mod", tuple(m.weight for m in lins) + tuple(m.bias for m in lins),
+                               lambda: (cat0([m.weight for m in lins]), cat0([m.bias for m in lins])))
+
+    def _patch_weight(self):
+        w = self.patch_embed.proj.weight
+        return self._fused.get("patch_w", w, lambda: w.detach().reshape(self.cfg["dim"], -1).contiguous())
 
     def joint_pos_embedding(self, frames: int, height: int, width: int) -> torch.Tensor:
         """[max_text + frames * height * width, D] bf16: the positional rows added to the joint sequence (diffusers 0.32.2
@@ -242,12 +237,13 @@ class CogVideoXTransformer3DModel(nn.Module):
         x = torch.empty(B, Sl, D, dtype=torch.bfloat16, device=hidden_states.device)
         pos = self.joint_pos_embedding(F, H // p, W // p)
         patches = ops.patchify(hidden_states, image_latents, B).view(B, Nv, -1)
+        patch_w = self._patch_weight()
         for b in range(B):
             if Ltl > 0:
                 ops.linear(encoder_hidden_states[b, t0:t0 + Ltl], self.patch_embed.text_proj.weight, self.patch_embed.text_proj.bias, out=x[b, :Ltl],
                            epilogue=ops.EPI_RESID, resid=pos[t0:t0 + Ltl])
             if v1 > v0:
-                ops.linear(patches[b, v0:v1], self._fused["patch_w"], self.patch_embed.proj.bias, out=x[b, Ltl:], epilogue=ops.EPI_RESID,
+                ops.linear(patches[b, v0:v1], patch_w, self.patch_embed.proj.bias, out=x[b, Ltl:], epilogue=ops.EPI_RESID,
                            resid=pos[Lt + v0:Lt + v1])
         if sp is not None and rope is not None:
             rope = (rope[0][v0:v1], rope[1][v0:v1])                 # RoPE rows of the local video tokens
@@ -264,7 +260,7 @@ class CogVideoXTransformer3DModel(nn.Module):
             """one of the block's large linears in the precision its site is set to"""
             if site not in fp8:
                 return ops.linear(inp, lin.weight, lin.bias, **kw)
-            w8, w_exp = self._fp8_weights.get(((site, layer), _wkey(lin.weight)), lambda: ops.quant_rows_e4m3(lin.weight.detach()))
+            w8, w_exp = self._fused.get((site, layer), lin.weight, lambda: ops.quant_rows_e4m3(lin.weight.detach()))
             return ops.linear_fp8(inp, w8, w_exp, lin.bias, **kw)
 
         for i, blk in enumerate(self.transformer_blocks):

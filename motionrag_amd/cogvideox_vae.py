@@ -25,8 +25,8 @@ import torch
 from torch import nn
 
 from . import ops
-from .dynamicrafter import _CACHE
-from .dynamicrafter_vae import DiagonalGaussianDistribution, _b
+from .dynamicrafter_vae import DiagonalGaussianDistribution
+from .layers import CACHE, bf16
 
 _KPAD = 64          # the implicit GEMM moves whole 64-channel K-tiles: 3 (RGB) and 16 (latent) channel inputs travel zero-padded
 
@@ -57,19 +57,19 @@ def _w27(mod: CogVideoXCausalConv3d, cout_pad: int = 0) -> Tuple[torch.Tensor, t
     conv = mod.conv
 
     def build():
-        w = _b(conv.weight).permute(0, 2, 3, 4, 1)
+        w = bf16(conv.weight).permute(0, 2, 3, 4, 1)
         w = _pad_channels(w).reshape(w.shape[0], -1)
-        b = _b(conv.bias)
+        b = bf16(conv.bias)
         extra = (-w.shape[0]) % 4 if cout_pad else 0
         if extra:
             w = torch.cat([w, torch.zeros(extra, w.shape[1], dtype=w.dtype, device=w.device)])
             b = torch.cat([b, torch.zeros(extra, dtype=b.dtype, device=b.device)])
         return w.contiguous(), b.contiguous()
-    return _CACHE.get(("cvx27", id(conv), cout_pad), (conv.weight, conv.bias), build)
+    return CACHE.get(("cvx27", id(conv), cout_pad), (conv.weight, conv.bias), build)
 
 
 def _w9(conv: nn.Conv2d) -> torch.Tensor:
-    return _CACHE.get(("cvx9", id(conv)), conv.weight, lambda: _b(conv.weight).permute(0, 2, 3, 1).reshape(conv.weight.shape[0], -1).contiguous())
+    return CACHE.get(("cvx9", id(conv)), conv.weight, lambda: bf16(conv.weight).permute(0, 2, 3, 1).reshape(conv.weight.shape[0], -1).contiguous())
 
 
 def _new_stack(T: int, H: int, W: int, C: int, device) -> torch.Tensor:
@@ -93,14 +93,14 @@ def _causal3(stack: torch.Tensor, mod: CogVideoXCausalConv3d, cache: Dict, resid
 
 def _cond_weights(norm: CogVideoXSpatialNorm3D) -> Tuple[torch.Tensor, torch.Tensor]:
     def build():
-        wy, wb = (_b(c.conv.weight).reshape(c.conv.weight.shape[0], -1) for c in (norm.conv_y, norm.conv_b))
+        wy, wb = (bf16(c.conv.weight).reshape(c.conv.weight.shape[0], -1) for c in (norm.conv_y, norm.conv_b))
         w = _pad_channels(torch.cat([wy, wb]))
-        return w.contiguous(), torch.cat([_b(norm.conv_y.conv.bias), _b(norm.conv_b.conv.bias)]).contiguous()
-    return _CACHE.get(("cvxyb", id(norm)), (norm.conv_y.conv.weight, norm.conv_b.conv.weight, norm.conv_y.conv.bias, norm.conv_b.conv.bias), build)
+        return w.contiguous(), torch.cat([bf16(norm.conv_y.conv.bias), bf16(norm.conv_b.conv.bias)]).contiguous()
+    return CACHE.get(("cvxyb", id(norm)), (norm.conv_y.conv.weight, norm.conv_b.conv.weight, norm.conv_y.conv.bias, norm.conv_b.conv.bias), build)
 
 
 def _w1(sc: nn.Conv3d) -> torch.Tensor:
-    return _CACHE.get(("cvx1", id(sc)), sc.weight, lambda: _b(sc.weight).reshape(sc.weight.shape[0], -1).contiguous())
+    return CACHE.get(("cvx1", id(sc)), sc.weight, lambda: bf16(sc.weight).reshape(sc.weight.shape[0], -1).contiguous())
 
 
 def _cond_maps(norm: CogVideoXSpatialNorm3D, zq64: torch.Tensor) -> torch.Tensor:
@@ -116,10 +116,10 @@ def _norm_into_stack(x: torch.Tensor, norm, zq64: Optional[torch.Tensor], groups
     stack = _new_stack(T, H, W, C, x.device)
     out = stack[2:].view(1, T * H * W, C)
     if zq64 is None:                                                         # encoder: plain GroupNorm over (T, H, W, C / G)
-        ops.groupnorm(x.view(1, T * H * W, C), _b(norm.weight), _b(norm.bias), groups, eps, silu=True, out=out)
+        ops.groupnorm(x.view(1, T * H * W, C), bf16(norm.weight), bf16(norm.bias), groups, eps, silu=True, out=out)
     else:
         shift = int(math.log2(H // zq64.shape[1]))
-        ops.groupnorm(x.view(1, T * H * W, C), _b(norm.norm_layer.weight), _b(norm.norm_layer.bias), groups, eps, silu=True, out=out,
+        ops.groupnorm(x.view(1, T * H * W, C), bf16(norm.norm_layer.weight), bf16(norm.norm_layer.bias), groups, eps, silu=True, out=out,
                       mod=_cond_maps(norm, zq64), mod_geom=(T, H, W, shift, T > 1 and T % 2 == 1))
     return stack
 
@@ -141,7 +141,7 @@ class CogVideoXResnetBlock3D(nn.Module):
         h = _causal3(_norm_into_stack(x, self.norm1, zq64, self.groups, self.eps), self.conv1, cache)
         stack = _norm_into_stack(h, self.norm2, zq64, self.groups, self.eps)
         if hasattr(self, "conv_shortcut"):
-            x = ops.linear(x, _w1(self.conv_shortcut), _b(self.conv_shortcut.bias))
+            x = ops.linear(x, _w1(self.conv_shortcut), bf16(self.conv_shortcut.bias))
         return _causal3(stack, self.conv2, cache, resid=x.contiguous())
 
 
@@ -220,7 +220,7 @@ class CogVideoXUpsample3D(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         T = x.shape[0]
-        y = ops.conv_implicit(x.contiguous(), _w9(self.conv), _b(self.conv.bias), ops.CONV_3X3, upsample=True)
+        y = ops.conv_implicit(x.contiguous(), _w9(self.conv), bf16(self.conv.bias), ops.CONV_3X3, upsample=True)
         if self.compress_time and T > 1:                                      # nearest x2 in time; with an odd frame count the first frame stays single
             y = y.index_select(0, _frame_doubling(T, y.device))
         return y
@@ -237,7 +237,7 @@ class CogVideoXDownsample3D(nn.Module):
             first, rest = (x[:1], x[1:]) if T % 2 else (x[:0], x)
             pairs = ops.weighted_sum(rest.reshape(rest.shape[0] // 2, 2, *rest.shape[1:]).contiguous(), None, div=2.0)
             x = torch.cat([first, pairs]) if T % 2 else pairs
-        return ops.conv_implicit(x.contiguous(), _w9(self.conv), _b(self.conv.bias), ops.CONV_3X3, stride=2, asym_pad=True)
+        return ops.conv_implicit(x.contiguous(), _w9(self.conv), bf16(self.conv.bias), ops.CONV_3X3, stride=2, asym_pad=True)
 
 
 class _Block(_Resnets):

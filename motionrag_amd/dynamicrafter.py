@@ -26,34 +26,7 @@ import torch
 from torch import nn
 
 from . import ops
-
-
-def _cat0(ts):
-    return torch.cat([t.detach() for t in ts], dim=0).contiguous()
-
-
-class _Cache:
-    """weights re-laid-out once per weight tensor: conv kernels as [Cout, (ky, kx, cin)] GEMM operands, fused K|V projections, GEGLU row
-    interleaves.  An entry is valid only for the SAME tensor object (weak reference: `id()` of a collected module can be reused), at the
-    same storage address, dtype and in-place version (`load_state_dict` copies in place)."""
-
-    def __init__(self):
-        self.d = {}
-
-    def get(self, key, ref, build):
-        """`ref`: the tensor -- or a tuple of ALL tensors (None entries allowed) -- that `build` reads: replacing or updating any one of
-        them in place invalidates the entry"""
-        import weakref
-        refs = tuple(r for r in (ref if isinstance(ref, (tuple, list)) else (ref,)) if r is not None)
-        tag = tuple((r.data_ptr(), r.dtype, r._version) for r in refs)
-        ent = self.d.get(key)
-        if ent is None or ent[0] != tag or any(w() is not r for w, r in zip(ent[1], refs)):
-            ent = (tag, tuple(weakref.ref(r) for r in refs), build())
-            self.d[key] = ent
-        return ent[2]
-
-
-_CACHE = _Cache()
+from .layers import CACHE, cat0, conv3x3, conv_t3, host_scalar, lin_w
 
 
 class TembBank:
@@ -66,7 +39,7 @@ class TembBank:
     def __init__(self, silu_emb: torch.Tensor, owner: nn.Module, linears):
         self.silu = silu_emb
         refs = tuple(t for lin in linears for t in (lin.weight, lin.bias))
-        w, b, offs = _CACHE.get(("tembbank", id(owner)), refs, lambda: (
+        w, b, offs = CACHE.get(("tembbank", id(owner)), refs, lambda: (
             torch.cat([lin.weight.detach() for lin in linears], dim=0).contiguous(),
             torch.cat([(lin.bias.detach() if lin.bias is not None else torch.zeros(lin.out_features, dtype=lin.weight.dtype, device=lin.weight.device))
                        for lin in linears], dim=0).contiguous(),
@@ -84,57 +57,6 @@ class TembBank:
 def temb_proj(silu_emb, lin: nn.Linear) -> torch.Tensor:
     """`lin(SiLU(emb))`: a slice of the step's TembBank, or the plain projection when a block is driven with a bare tensor (unit tests)"""
     return silu_emb.proj(lin) if isinstance(silu_emb, TembBank) else ops.linear(silu_emb, lin.weight, lin.bias)
-
-
-def _tanh_scalar(p: torch.Tensor) -> float:
-    """tanh of a learnable scalar gate (attention.py:200-202, 216-218) as a host float, read back ONCE per weight version: a `.item()` per
-    attention call is a host sync per layer and cannot be captured in a HIP graph"""
-    return _CACHE.get(("tanh", id(p)), p, lambda: float(torch.tanh(p.detach().float()).item()))
-
-
-def conv3x3(x: torch.Tensor, conv: nn.Conv2d, *, stride: int = 1, upsample: bool = False, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """x [N, H, W, Cin] -> [N, Ho, Wo, Cout]: implicit GEMM over gathered rows; `resid` (same shape as the output) fused in the epilogue."""
-    N, H, W, C = x.shape
-    cout = conv.weight.shape[0]
-    kp = ops._kpad(9 * C)
-
-    def build():
-        w = conv.weight.detach().permute(0, 2, 3, 1).reshape(cout, 9 * C)          # [Cout, Cin, ky, kx] -> [Cout, (ky, kx, cin)]
-        if kp != 9 * C:
-            w = torch.cat([w, torch.zeros(cout, kp - 9 * C, dtype=w.dtype, device=w.device)], dim=1)
-        return w.contiguous()
-
-    wk = _CACHE.get(("c3", id(conv)), conv.weight, build)
-    if C % 64 == 0:                                                                 # implicit GEMM: the GEMM's DMA gathers the taps itself
-        return ops.conv_implicit(x.contiguous(), wk, conv.bias, ops.CONV_3X3, stride=stride, upsample=upsample,
-                                 resid=resid.contiguous() if resid is not None else None)
-    rows = ops.im2col3x3(x, stride=stride, upsample=upsample)
-    Hi, Wi = (2 * H, 2 * W) if upsample else (H, W)
-    Ho, Wo = (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
-    if resid is not None:
-        y = ops.linear(rows, wk, conv.bias, epilogue=ops.EPI_RESID, resid=resid.reshape(-1, cout))
-    else:
-        y = ops.linear(rows, wk, conv.bias)
-    return y.view(N, Ho, Wo, cout)
-
-
-def conv_t3(x: torch.Tensor, conv: nn.Conv3d, B: int, T: int, *, resid: Optional[torch.Tensor] = None, acc_scale: float = 1.0) -> torch.Tensor:
-    """nn.Conv3d((3,1,1), padding (1,0,0)) on x [(b t), HW, C]; with `resid`: resid + acc_scale * conv(x)"""
-    C = x.shape[-1]
-    cout = conv.weight.shape[0]
-    wk = _CACHE.get(("t3", id(conv)), conv.weight, lambda: conv.weight.detach()[:, :, :, 0, 0].permute(0, 2, 1).reshape(cout, 3 * C).contiguous())
-    if C % 64 == 0:
-        return ops.conv_implicit(x.contiguous(), wk, conv.bias, ops.CONV_T3, frames=T, resid=resid.contiguous() if resid is not None else None, acc_scale=acc_scale)
-    rows = ops.unfold_t3(x, B, T)
-    if resid is not None:
-        return ops.linear(rows, wk, conv.bias, epilogue=ops.EPI_RESID, resid=resid.reshape(-1, cout), acc_scale=acc_scale).view(x.shape[0], x.shape[1], cout)
-    return ops.linear(rows, wk, conv.bias).view(x.shape[0], x.shape[1], cout)
-
-
-def _lin_w(m) -> torch.Tensor:
-    """nn.Linear or 1x1 Conv1d / Conv2d weight as [out, in]"""
-    w = m.weight
-    return w if w.dim() == 2 else _CACHE.get(("w2", id(m)), w, lambda: w.detach().reshape(w.shape[0], w.shape[1]).contiguous())
 
 
 # ------------------------------------------------------------------------------------------------------ attention
@@ -184,7 +106,7 @@ class CrossAttention(nn.Module):
                 self.register_parameter("alpha_action", nn.Parameter(torch.tensor(0.0)))
 
     def _kv(self, key, wk, wv, ctx):
-        w = _CACHE.get((key, id(self)), (wk.weight, wv.weight), lambda: _cat0([wk.weight, wv.weight]))
+        w = CACHE.get((key, id(self)), (wk.weight, wv.weight), lambda: cat0([wk.weight, wv.weight]))
         kv = ops.linear(ctx.contiguous(), w)
         return kv[..., : self.inner].unflatten(-1, (self.heads, 64)), kv[..., self.inner:].unflatten(-1, (self.heads, 64))
 
@@ -198,7 +120,7 @@ class CrossAttention(nn.Module):
         H, inner = self.heads, self.inner
         Nb, L, _ = x.shape
         if context is None:                                                         # spatial / temporal self-attention  :175-183
-            w = _CACHE.get(("qkv", id(self)), (self.to_q.weight, self.to_k.weight, self.to_v.weight), lambda: _cat0([self.to_q.weight, self.to_k.weight, self.to_v.weight]))
+            w = CACHE.get(("qkv", id(self)), (self.to_q.weight, self.to_k.weight, self.to_v.weight), lambda: cat0([self.to_q.weight, self.to_k.weight, self.to_v.weight]))
             qkv = ops.linear(x, w)
             if temporal is None:
                 q5 = qkv.view(Nb, L, 3, H, 64)
@@ -218,12 +140,12 @@ class CrossAttention(nn.Module):
             out = ops.attention(q, k, v, kv_batch_div=Nb // k.shape[0])             # :189
             if self.image_cross_attention:                                          # :191-204
                 k, v = self._kv("kv_ip", self.to_k_ip, self.to_v_ip, context["image"])
-                s = self.image_cross_attention_scale * ((_tanh_scalar(self.alpha) + 1) if self.image_cross_attention_scale_learnable else 1.0)
+                s = self.image_cross_attention_scale * ((host_scalar(torch.tanh, self.alpha) + 1) if self.image_cross_attention_scale_learnable else 1.0)
                 ops.attention(q, k, v, out=out, resid=out, kv_batch_div=Nb // k.shape[0], out_scale=float(s))
             if self.action_cross_attention:                                         # :206-220  q_a = to_q_a(out)
                 q_a = ops.linear(out, self.to_q_a.weight).view(Nb, L, H, 64)
                 k, v = self._kv("kv_a", self.to_k_a, self.to_v_a, context["action"])
-                s = self.action_cross_attention_scale * ((_tanh_scalar(self.alpha_action) + 1) if self.action_cross_attention_scale_learnable else 1.0)
+                s = self.action_cross_attention_scale * ((host_scalar(torch.tanh, self.alpha_action) + 1) if self.action_cross_attention_scale_learnable else 1.0)
                 ops.attention(q_a, k, v, out=out, resid=out, kv_batch_div=Nb // k.shape[0], out_scale=float(s))
         if resid is not None:
             return ops.linear(out, self.to_out[0].weight, self.to_out[0].bias, epilogue=ops.EPI_RESID, resid=resid)
@@ -250,7 +172,7 @@ class FeedForward(nn.Module):
 
     def forward(self, x, resid=None):
         pj = self.net[0].proj
-        w, b = _CACHE.get(("geglu", id(pj)), (pj.weight, pj.bias), lambda: ops.geglu_interleave(pj.weight, pj.bias))
+        w, b = CACHE.get(("geglu", id(pj)), (pj.weight, pj.bias), lambda: ops.geglu_interleave(pj.weight, pj.bias))
         h = ops.linear(x, w, b, epilogue=ops.EPI_GEGLU)                             # value * gelu(gate) in the GEMM epilogue
         if resid is not None:
             return ops.linear(h, self.net[2].weight, self.net[2].bias, epilogue=ops.EPI_RESID, resid=resid)
@@ -334,10 +256,10 @@ class TemporalTransformer(nn.Module):
         N, H, W, C = x.shape
         t, hw = N // b, H * W
         y = ops.groupnorm(x.view(b, t * hw, C), self.norm.weight, self.norm.bias, 32, self.norm.eps).view(N, hw, C)
-        y = ops.linear(y, _lin_w(self.proj_in), self.proj_in.bias)
+        y = ops.linear(y, lin_w(self.proj_in), self.proj_in.bias)
         for blk in self.transformer_blocks:
             y = blk(y, context=None, temporal=(b, t, hw))
-        return ops.linear(y, _lin_w(self.proj_out), self.proj_out.bias, epilogue=ops.EPI_RESID, resid=x.view(N, hw, C)).view(N, H, W, C)
+        return ops.linear(y, lin_w(self.proj_out), self.proj_out.bias, epilogue=ops.EPI_RESID, resid=x.view(N, hw, C)).view(N, H, W, C)
 
 
 # ------------------------------------------------------------------------------------------------------ conv blocks
@@ -398,7 +320,7 @@ class ResBlock(nn.Module):
         if isinstance(self.skip_connection, nn.Identity):
             skip = x
         elif self.skip_connection.kernel_size == (1, 1):
-            skip = ops.linear(x, _lin_w(self.skip_connection), self.skip_connection.bias)
+            skip = ops.linear(x, lin_w(self.skip_connection), self.skip_connection.bias)
         else:
             skip = conv3x3(x, self.skip_connection)
         h = conv3x3(h, self.out_layers[3], resid=skip)                                                          # skip + h  :231

@@ -22,14 +22,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .dynamicrafter import _CACHE, _lin_w, conv3x3
-
-
-def _b(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    if t is None:
-        return None
-    t = t.detach()
-    return t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)
+from .layers import CACHE, _conv_small_cin, bf16, conv3x3, lin_w
 
 
 def Normalize(in_channels: int, num_groups: int = 32) -> nn.GroupNorm:
@@ -40,7 +33,7 @@ def Normalize(in_channels: int, num_groups: int = 32) -> nn.GroupNorm:
 def _gn_swish(x: torch.Tensor, gn: nn.GroupNorm, silu: bool = True) -> torch.Tensor:
     """x [N, H, W, C] -> same; GroupNorm over (H W, C / G) per (n, group) [+ x * sigmoid(x)]"""
     N, H, W, C = x.shape
-    return ops.groupnorm(x.view(N, H * W, C), _b(gn.weight), _b(gn.bias), gn.num_groups, gn.eps, silu=silu).view(N, H, W, C)
+    return ops.groupnorm(x.view(N, H * W, C), bf16(gn.weight), bf16(gn.bias), gn.num_groups, gn.eps, silu=silu).view(N, H, W, C)
 
 
 class ResnetBlock(nn.Module):
@@ -69,7 +62,7 @@ class ResnetBlock(nn.Module):
             if self.use_conv_shortcut:
                 x = conv3x3(x, self.conv_shortcut)
             else:
-                x = ops.linear(x, _b(_lin_w(self.nin_shortcut)), _b(self.nin_shortcut.bias))
+                x = ops.linear(x, bf16(lin_w(self.nin_shortcut)), bf16(self.nin_shortcut.bias))
         return conv3x3(h, self.conv2, resid=x)                               # x + h in the convolution's epilogue
 
 
@@ -89,17 +82,17 @@ class AttnBlock(nn.Module):
         N, H, W, C = x.shape
         S = H * W
         h = _gn_swish(x, self.norm, silu=False).view(N, S, C)
-        q = ops.linear(h, _b(_lin_w(self.q)), _b(self.q.bias))                                   # [N, S, C]
-        k = ops.linear(h, _b(_lin_w(self.k)), _b(self.k.bias))
-        wv = _b(_lin_w(self.v))
+        q = ops.linear(h, bf16(lin_w(self.q)), bf16(self.q.bias))                                   # [N, S, C]
+        k = ops.linear(h, bf16(lin_w(self.k)), bf16(self.k.bias))
+        wv = bf16(lin_w(self.v))
         a = torch.empty(N, S, C, dtype=torch.bfloat16, device=x.device)
         scores = torch.empty(S, S, dtype=torch.bfloat16, device=x.device)                         # one frame at a time: 170 MB at 72 x 128
         for n in range(N):
             ops.linear(q[n], k[n], out=scores)                                                    # w_[i, j] = sum_c q[i, c] k[j, c]        (:67)
             ops.softmax_rows(scores, scale=float(C) ** -0.5, out=scores)                          # * c^-0.5, softmax over j                (:68-69)
             vt = ops.linear(wv, h[n])                                                             # V^T [C, S] = Wv h^T: no transpose pass
-            ops.linear(scores, vt, _b(self.v.bias), out=a[n])                                     # sum_j w_[i, j] v[j, c] (+ b_v: rows sum to 1)  (:72-75)
-        return ops.linear(a, _b(_lin_w(self.proj_out)), _b(self.proj_out.bias), epilogue=ops.EPI_RESID, resid=x.view(N, S, C)).view(N, H, W, C)
+            ops.linear(scores, vt, bf16(self.v.bias), out=a[n])                                     # sum_j w_[i, j] v[j, c] (+ b_v: rows sum to 1)  (:72-75)
+        return ops.linear(a, bf16(lin_w(self.proj_out)), bf16(self.proj_out.bias), epilogue=ops.EPI_RESID, resid=x.view(N, S, C)).view(N, H, W, C)
 
 
 class Upsample(nn.Module):
@@ -186,13 +179,13 @@ class Decoder(nn.Module):
         def build():
             cout, cin = conv.weight.shape[:2]
             pad = (-cout) % 4
-            w = _b(conv.weight).permute(0, 2, 3, 1).reshape(cout, 9 * cin)
-            b = _b(conv.bias)
+            w = bf16(conv.weight).permute(0, 2, 3, 1).reshape(cout, 9 * cin)
+            b = bf16(conv.bias)
             if pad:
                 w = torch.cat([w, torch.zeros(pad, 9 * cin, dtype=w.dtype, device=w.device)], 0)
                 b = torch.cat([b, torch.zeros(pad, dtype=b.dtype, device=b.device)], 0)
             return w.contiguous(), b.contiguous()
-        wk, bk = _CACHE.get(("vae_out", id(conv)), (conv.weight, conv.bias), build)
+        wk, bk = CACHE.get(("vae_out", id(conv)), (conv.weight, conv.bias), build)
         y = ops.conv_implicit(h.contiguous(), wk, bk, ops.CONV_3X3)
         return y[..., :self.out_ch]
 
@@ -212,23 +205,8 @@ class Downsample(nn.Module):
         C = x.shape[-1]
         if C % 64:
             raise NotImplementedError("Downsample: channel counts are multiples of 64 on the reference's path")
-        wk = _CACHE.get(("c3", id(conv)), conv.weight, lambda: _b(conv.weight).permute(0, 2, 3, 1).reshape(conv.weight.shape[0], 9 * C).contiguous())
-        return ops.conv_implicit(x.contiguous(), wk, _b(conv.bias), ops.CONV_3X3, stride=2, asym_pad=True)
-
-
-def _conv_small_cin(z: torch.Tensor, conv: nn.Conv2d, tag: str) -> torch.Tensor:
-    """3x3 convolution from 3 (RGB) or 4 (latent) channels: the row gather moves 16-byte (8-channel) granules, so the input and the kernel get zero channels"""
-    N, H, W, cz = z.shape
-    cp = (cz + 7) // 8 * 8
-    if cp != cz:
-        z = torch.nn.functional.pad(z, (0, cp - cz))
-    kp = ops._kpad(9 * cp)
-
-    def build():
-        w = torch.nn.functional.pad(_b(conv.weight), (0, 0, 0, 0, 0, cp - cz)).permute(0, 2, 3, 1).reshape(conv.weight.shape[0], 9 * cp)
-        return torch.nn.functional.pad(w, (0, kp - 9 * cp)).contiguous()
-    wk = _CACHE.get((tag, id(conv), cp), conv.weight, build)
-    return ops.linear(ops.im2col3x3(z.contiguous()), wk, _b(conv.bias)).view(N, H, W, -1)
+        wk = CACHE.get(("c3", id(conv)), conv.weight, lambda: bf16(conv.weight).permute(0, 2, 3, 1).reshape(conv.weight.shape[0], 9 * C).contiguous())
+        return ops.conv_implicit(x.contiguous(), wk, bf16(conv.bias), ops.CONV_3X3, stride=2, asym_pad=True)
 
 
 class Encoder(nn.Module):
@@ -308,7 +286,7 @@ class AutoencoderKL(nn.Module):
             raise ops.HipOnly("AutoencoderKL.encode: GPU tensors only")
         xc = x.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()
         h = self.encoder(xc)
-        moments = ops.linear(h, _b(_lin_w(self.quant_conv)), _b(self.quant_conv.bias))
+        moments = ops.linear(h, bf16(lin_w(self.quant_conv)), bf16(self.quant_conv.bias))
         return DiagonalGaussianDistribution(moments.permute(0, 3, 1, 2))
 
     @torch.no_grad()
@@ -327,7 +305,7 @@ class AutoencoderKL(nn.Module):
         outs = []
         for i in range(0, N, chunk):
             zc = z[i:i + chunk].to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()       # channels-last rows (a few KB per frame)
-            zc = ops.linear(zc, _b(_lin_w(self.post_quant_conv)), _b(self.post_quant_conv.bias))
+            zc = ops.linear(zc, bf16(lin_w(self.post_quant_conv)), bf16(self.post_quant_conv.bias))
             outs.append(self.decoder(zc).permute(0, 3, 1, 2))
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 

@@ -23,7 +23,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .dynamicrafter import _CACHE
+from .layers import CACHE, Holder, bf16, prenorm_block
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -232,11 +232,6 @@ def sinusoid_table(n_position: int, d_hid: int) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------------------- ViT bodies
-def _b(t: torch.Tensor) -> torch.Tensor:
-    t = t.detach()
-    return t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)
-
-
 class _SelfAttention(nn.Module):
     """`…attention.attention`: query / key / value weights + biases.  Internal layout = transformers 4.44.2's VideoMAE one (weights without bias,
     `q_bias` / `v_bias` parameters) plus a `k_bias`; the 5.x / DINOv2 layout (`query.bias`, `key.bias`, `value.bias`) is mapped on load."""
@@ -261,20 +256,16 @@ class _SelfAttention(nn.Module):
         parts = (self.query.weight, self.key.weight, self.value.weight, self.q_bias, self.k_bias, self.v_bias)
 
         def build():
-            w = torch.cat([_b(self.query.weight), _b(self.key.weight), _b(self.value.weight)], 0).contiguous()
-            b = None if self.q_bias is None else torch.cat([_b(self.q_bias), _b(self.k_bias), _b(self.v_bias)], 0).contiguous()
+            w = torch.cat([bf16(self.query.weight), bf16(self.key.weight), bf16(self.value.weight)], 0).contiguous()
+            b = None if self.q_bias is None else torch.cat([bf16(self.q_bias), bf16(self.k_bias), bf16(self.v_bias)], 0).contiguous()
             return w, b
-        return _CACHE.get(("vit_qkv", id(self)), parts, build)
-
-
-class _Holder(nn.Module):
-    pass
+        return CACHE.get(("vit_qkv", id(self)), parts, build)
 
 
 def _attn_block(dim: int, bias: bool = True) -> nn.Module:
-    m = _Holder()
+    m = Holder()
     m.attention = _SelfAttention(dim, bias)
-    m.output = _Holder()
+    m.output = Holder()
     m.output.dense = nn.Linear(dim, dim)
     return m
 
@@ -285,36 +276,14 @@ class _LayerScale(nn.Module):
         self.lambda1 = nn.Parameter(init * torch.ones(dim))
 
 
-def _layer_forward(x: torch.Tensor, heads: int, eps: float, n1: nn.LayerNorm, att: nn.Module, n2: nn.LayerNorm, fc1: nn.Linear, fc2: nn.Linear,
-                   ls1: Optional[_LayerScale], ls2: Optional[_LayerScale]) -> torch.Tensor:
-    """pre-norm ViT block: x + [ls1 *] proj(attn(norm1(x))), then x + [ls2 *] fc2(gelu(fc1(norm2(x)))); every residual rides in a GEMM epilogue"""
-    N, S, D = x.shape
-    h = ops.layernorm(x, _b(n1.weight), _b(n1.bias), eps)
-    w, b = att.attention.fused()
-    qkv = ops.linear(h, w, b).view(N, S, 3, heads, 64)
-    a = ops.attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2])
-    od = att.output.dense
-    if ls1 is None:
-        x = ops.linear(a, _b(od.weight), _b(od.bias), epilogue=ops.EPI_RESID, resid=x)
-    else:
-        g = _b(ls1.lambda1)
-        x = ops.linear(a, _b(od.weight), _b(od.bias), epilogue=ops.EPI_GATE_RESID, resid=x, gate0=g, gate1=g, rows_per_batch=N * S, split=0, gate_stride=0)
-    h = ops.layernorm(x, _b(n2.weight), _b(n2.bias), eps)
-    h = ops.linear(h, _b(fc1.weight), _b(fc1.bias), epilogue=ops.EPI_GELU_ERF)
-    if ls2 is None:
-        return ops.linear(h, _b(fc2.weight), _b(fc2.bias), epilogue=ops.EPI_RESID, resid=x)
-    g = _b(ls2.lambda1)
-    return ops.linear(h, _b(fc2.weight), _b(fc2.bias), epilogue=ops.EPI_GATE_RESID, resid=x, gate0=g, gate1=g, rows_per_batch=N * S, split=0, gate_stride=0)
-
-
 class _VideoMAELayer(nn.Module):
     def __init__(self, dim: int, inter: int, eps: float, qkv_bias: bool):
         super().__init__()
         self.attention = _attn_block(dim, qkv_bias)
         self.layernorm_before = nn.LayerNorm(dim, eps=eps)
         self.layernorm_after = nn.LayerNorm(dim, eps=eps)
-        self.intermediate = _Holder(); self.intermediate.dense = nn.Linear(dim, inter)
-        self.output = _Holder(); self.output.dense = nn.Linear(inter, dim)
+        self.intermediate = Holder(); self.intermediate.dense = nn.Linear(dim, inter)
+        self.output = Holder(); self.output.dense = nn.Linear(inter, dim)
 
 
 class VideoMAEModel(nn.Module):
@@ -330,10 +299,10 @@ class VideoMAEModel(nn.Module):
         self.heads, self.eps = num_attention_heads, layer_norm_eps
         self.patch = (tubelet_size, patch_size, patch_size)
         self.num_frames, self.image_size, self.hidden_size = num_frames, image_size, hidden_size
-        self.embeddings = _Holder()
-        self.embeddings.patch_embeddings = _Holder()
+        self.embeddings = Holder()
+        self.embeddings.patch_embeddings = Holder()
         self.embeddings.patch_embeddings.projection = nn.Conv3d(num_channels, hidden_size, self.patch, stride=self.patch)
-        self.encoder = _Holder()
+        self.encoder = Holder()
         self.encoder.layer = nn.ModuleList(_VideoMAELayer(hidden_size, intermediate_size, layer_norm_eps, qkv_bias) for _ in range(num_hidden_layers))
         self.layernorm = None if use_mean_pooling else nn.LayerNorm(hidden_size, eps=layer_norm_eps)
         self._pos = {}
@@ -349,15 +318,16 @@ class VideoMAEModel(nn.Module):
         conv = self.embeddings.patch_embeddings.projection
 
         def build():
-            w = _b(conv.weight).reshape(conv.weight.shape[0], -1)
+            w = bf16(conv.weight).reshape(conv.weight.shape[0], -1)
             return torch.nn.functional.pad(w, (0, rows.shape[1] - w.shape[1])).contiguous()
-        w = _CACHE.get(("vit_patch", id(conv), rows.shape[1]), conv.weight, build)
-        x = ops.linear(rows, w, _b(conv.bias)).view(batch, -1, self.hidden_size)
+        w = CACHE.get(("vit_patch", id(conv), rows.shape[1]), conv.weight, build)
+        x = ops.linear(rows, w, bf16(conv.bias)).view(batch, -1, self.hidden_size)
         x = assemble_tokens(x, None, self._position_table(x.shape[1], x.device))
         for L in self.encoder.layer:
-            x = _layer_forward(x, self.heads, self.eps, L.layernorm_before, L.attention, L.layernorm_after, L.intermediate.dense, L.output.dense, None, None)
+            x = prenorm_block(x, self.heads, L.layernorm_before, *L.attention.attention.fused(), L.attention.output.dense, L.layernorm_after, L.intermediate.dense,
+                              L.output.dense, eps=self.eps)
         if self.layernorm is not None:
-            x = ops.layernorm(x, _b(self.layernorm.weight), _b(self.layernorm.bias), self.eps)
+            x = ops.layernorm(x, bf16(self.layernorm.weight), bf16(self.layernorm.bias), self.eps)
         return x
 
     def forward(self, pixel_values: torch.Tensor) -> torch.Tensor:
@@ -379,7 +349,7 @@ class _Dinov2Layer(nn.Module):
         self.attention = _attn_block(dim, True)
         self.layer_scale1 = _LayerScale(dim, ls_init)
         self.norm2 = nn.LayerNorm(dim, eps=eps)
-        self.mlp = _Holder(); self.mlp.fc1 = nn.Linear(dim, inter); self.mlp.fc2 = nn.Linear(inter, dim)
+        self.mlp = Holder(); self.mlp.fc1 = nn.Linear(dim, inter); self.mlp.fc2 = nn.Linear(inter, dim)
         self.layer_scale2 = _LayerScale(dim, ls_init)
 
 
@@ -397,13 +367,13 @@ class Dinov2Model(nn.Module):
             raise NotImplementedError("SwiGLU variant (dinov2-giant) is not on the reference's path")
         self.heads, self.eps, self.hidden_size, self.patch_size, self.pos_dialect = num_attention_heads, layer_norm_eps, hidden_size, patch_size, pos_dialect
         g = image_size // patch_size
-        self.embeddings = _Holder()
+        self.embeddings = Holder()
         self.embeddings.cls_token = nn.Parameter(torch.randn(1, 1, hidden_size))
         self.embeddings.mask_token = nn.Parameter(torch.zeros(1, hidden_size))
         self.embeddings.position_embeddings = nn.Parameter(torch.randn(1, g * g + 1, hidden_size))
-        self.embeddings.patch_embeddings = _Holder()
+        self.embeddings.patch_embeddings = Holder()
         self.embeddings.patch_embeddings.projection = nn.Conv2d(num_channels, hidden_size, patch_size, stride=patch_size)
-        self.encoder = _Holder()
+        self.encoder = Holder()
         self.encoder.layer = nn.ModuleList(_Dinov2Layer(hidden_size, int(hidden_size * mlp_ratio), layer_norm_eps, layerscale_value) for _ in range(num_hidden_layers))
         self.layernorm = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
 
@@ -426,21 +396,22 @@ class Dinov2Model(nn.Module):
                         raise ValueError("position-table interpolation produced an unexpected grid")
                 pos = torch.cat([pos[:, :1], patch.permute(0, 2, 3, 1).reshape(1, gh * gw, -1)], dim=1)
             return pos[0].to(torch.bfloat16).contiguous()
-        return _CACHE.get(("dino_pos", id(self), gh, gw, self.pos_dialect), pe, build)
+        return CACHE.get(("dino_pos", id(self), gh, gw, self.pos_dialect), pe, build)
 
     def forward_rows(self, rows: torch.Tensor, batch: int, gh: int, gw: int) -> torch.Tensor:
         conv = self.embeddings.patch_embeddings.projection
 
         def build():
-            w = _b(conv.weight).reshape(conv.weight.shape[0], -1)
+            w = bf16(conv.weight).reshape(conv.weight.shape[0], -1)
             return torch.nn.functional.pad(w, (0, rows.shape[1] - w.shape[1])).contiguous()
-        w = _CACHE.get(("vit_patch", id(conv), rows.shape[1]), conv.weight, build)
-        x = ops.linear(rows, w, _b(conv.bias)).view(batch, gh * gw, self.hidden_size)
-        cls = _CACHE.get(("dino_cls", id(self)), self.embeddings.cls_token, lambda: _b(self.embeddings.cls_token).reshape(1, -1).contiguous())
+        w = CACHE.get(("vit_patch", id(conv), rows.shape[1]), conv.weight, build)
+        x = ops.linear(rows, w, bf16(conv.bias)).view(batch, gh * gw, self.hidden_size)
+        cls = CACHE.get(("dino_cls", id(self)), self.embeddings.cls_token, lambda: bf16(self.embeddings.cls_token).reshape(1, -1).contiguous())
         x = assemble_tokens(x, cls, self._position_table(gh, gw))
         for L in self.encoder.layer:
-            x = _layer_forward(x, self.heads, self.eps, L.norm1, L.attention, L.norm2, L.mlp.fc1, L.mlp.fc2, L.layer_scale1, L.layer_scale2)
-        return ops.layernorm(x, _b(self.layernorm.weight), _b(self.layernorm.bias), self.eps)
+            x = prenorm_block(x, self.heads, L.norm1, *L.attention.attention.fused(), L.attention.output.dense, L.norm2, L.mlp.fc1, L.mlp.fc2, eps=self.eps,
+                              ls1=L.layer_scale1, ls2=L.layer_scale2)
+        return ops.layernorm(x, bf16(self.layernorm.weight), bf16(self.layernorm.bias), self.eps)
 
     def forward(self, pixel_values: torch.Tensor) -> torch.Tensor:
         """already-normalised `pixel_values` [B, C, H, W]"""

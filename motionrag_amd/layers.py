@@ -1,0 +1,152 @@
+"""What the model files share: the derived-weight cache, the bf16 view of a parameter, the empty state-dict namespace, the 3x3 / (3,1,1)
+convolutions as GEMMs and the pre-LayerNorm transformer block.  Host plumbing only: every launch goes through `ops`."""
+from __future__ import annotations
+
+import weakref
+from typing import Optional
+
+import torch
+from torch import nn
+
+from . import ops
+
+
+class WeightCache:
+    """weights re-laid-out once per weight tensor: conv kernels as [Cout, (ky, kx, cin)] GEMM operands, fused Q|K|V projections, GEGLU row
+    interleaves, folded motion keys.  An entry is valid only for the SAME tensor objects (weak references: `id()` and the storage address of
+    a collected tensor can be reused), at the same storage address, dtype and in-place version (`load_state_dict` copies in place).  It
+    holds its tensors weakly and is dropped when any of them is collected, so the derived copy does not outlive the module it came from."""
+
+    def __init__(self):
+        self.d = {}
+
+    def get(self, key, refs, build):
+        """`refs`: the tensor -- or a tuple of ALL tensors (None entries allowed) -- that `build` reads: replacing or updating any one of
+        them in place invalidates the entry, which `build()` then replaces under `key`"""
+        refs = tuple(r for r in (refs if isinstance(refs, (tuple, list)) else (refs,)) if r is not None)
+        tag = tuple((r.data_ptr(), r.dtype, r._version) for r in refs)
+        ent = self.d.get(key)
+        if ent is None or ent[0] != tag or any(w() is not r for w, r in zip(ent[1], refs)):
+            token, cache = object(), weakref.ref(self)
+
+            def drop(_):
+                # a collected tensor drops ITS entry only: one rebuilt since for live tensors under the same key carries another token
+                c = cache()
+                if c is not None and key in c.d and c.d[key][3] is token:
+                    del c.d[key]
+            ent = (tag, tuple(weakref.ref(r, drop) for r in refs), build(), token)
+            self.d[key] = ent
+        return ent[2]
+
+    def clear(self):
+        self.d.clear()
+
+
+CACHE = WeightCache()          # the model files' cache (keys carry the owner's id()); the attention processors keep one per instance
+
+
+def bf16(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    t = t.detach()
+    return t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)
+
+
+class Holder(nn.Module):
+    """empty module: a namespace that gives its children the checkpoint's state-dict keys"""
+
+
+def cat0(ts):
+    return torch.cat([t.detach() for t in ts], dim=0).contiguous()
+
+
+def lin_w(m) -> torch.Tensor:
+    """nn.Linear or 1x1 Conv1d / Conv2d weight as [out, in]"""
+    w = m.weight
+    return w if w.dim() == 2 else CACHE.get(("w2", id(m)), w, lambda: w.detach().reshape(w.shape[0], w.shape[1]).contiguous())
+
+
+def host_scalar(fn, p: torch.Tensor) -> float:
+    """`fn` (torch.tanh, torch.sigmoid) of a learnable scalar gate as a host float, read back ONCE per weight version: a `.item()` per
+    call is a host sync per layer and cannot be captured in a HIP graph"""
+    return CACHE.get(("scalar", fn, id(p)), p, lambda: float(fn(p.detach().float()).item()))
+
+
+def conv3x3(x: torch.Tensor, conv: nn.Conv2d, *, stride: int = 1, upsample: bool = False, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [N, H, W, Cin] -> [N, Ho, Wo, Cout]: implicit GEMM over gathered rows; `resid` (same shape as the output) fused in the epilogue."""
+    N, H, W, C = x.shape
+    cout = conv.weight.shape[0]
+    kp = ops._kpad(9 * C)
+
+    def build():
+        w = conv.weight.detach().permute(0, 2, 3, 1).reshape(cout, 9 * C)          # [Cout, Cin, ky, kx] -> [Cout, (ky, kx, cin)]
+        if kp != 9 * C:
+            w = torch.cat([w, torch.zeros(cout, kp - 9 * C, dtype=w.dtype, device=w.device)], dim=1)
+        return w.contiguous()
+
+    wk = CACHE.get(("c3", id(conv)), conv.weight, build)
+    if C % 64 == 0:                                                                 # implicit GEMM: the GEMM's DMA gathers the taps itself
+        return ops.conv_implicit(x.contiguous(), wk, conv.bias, ops.CONV_3X3, stride=stride, upsample=upsample,
+                                 resid=resid.contiguous() if resid is not None else None)
+    rows = ops.im2col3x3(x, stride=stride, upsample=upsample)
+    Hi, Wi = (2 * H, 2 * W) if upsample else (H, W)
+    Ho, Wo = (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
+    if resid is not None:
+        y = ops.linear(rows, wk, conv.bias, epilogue=ops.EPI_RESID, resid=resid.reshape(-1, cout))
+    else:
+        y = ops.linear(rows, wk, conv.bias)
+    return y.view(N, Ho, Wo, cout)
+
+
+def conv_t3(x: torch.Tensor, conv: nn.Conv3d, B: int, T: int, *, resid: Optional[torch.Tensor] = None, acc_scale: float = 1.0) -> torch.Tensor:
+    """nn.Conv3d((3,1,1), padding (1,0,0)) on x [(b t), HW, C]; with `resid`: resid + acc_scale * conv(x)"""
+    C = x.shape[-1]
+    cout = conv.weight.shape[0]
+    wk = CACHE.get(("t3", id(conv)), conv.weight, lambda: conv.weight.detach()[:, :, :, 0, 0].permute(0, 2, 1).reshape(cout, 3 * C).contiguous())
+    if C % 64 == 0:
+        return ops.conv_implicit(x.contiguous(), wk, conv.bias, ops.CONV_T3, frames=T, resid=resid.contiguous() if resid is not None else None, acc_scale=acc_scale)
+    rows = ops.unfold_t3(x, B, T)
+    if resid is not None:
+        return ops.linear(rows, wk, conv.bias, epilogue=ops.EPI_RESID, resid=resid.reshape(-1, cout), acc_scale=acc_scale).view(x.shape[0], x.shape[1], cout)
+    return ops.linear(rows, wk, conv.bias).view(x.shape[0], x.shape[1], cout)
+
+
+def _conv_small_cin(z: torch.Tensor, conv: nn.Conv2d, tag: str) -> torch.Tensor:
+    """3x3 convolution from 3 (RGB) or 4 (latent) channels: the row gather moves 16-byte (8-channel) granules, so the input and the kernel get zero channels"""
+    N, H, W, cz = z.shape
+    cp = (cz + 7) // 8 * 8
+    if cp != cz:
+        z = torch.nn.functional.pad(z, (0, cp - cz))
+    kp = ops._kpad(9 * cp)
+
+    def build():
+        w = torch.nn.functional.pad(bf16(conv.weight), (0, 0, 0, 0, 0, cp - cz)).permute(0, 2, 3, 1).reshape(conv.weight.shape[0], 9 * cp)
+        return torch.nn.functional.pad(w, (0, kp - 9 * cp)).contiguous()
+    wk = CACHE.get((tag, id(conv), cp), conv.weight, build)
+    return ops.linear(ops.im2col3x3(z.contiguous()), wk, bf16(conv.bias)).view(N, H, W, -1)
+
+
+def prenorm_block(x: torch.Tensor, heads: int, ln1: nn.LayerNorm, qkv_w: torch.Tensor, qkv_b: Optional[torch.Tensor], out_proj: nn.Linear, ln2: nn.LayerNorm,
+                  fc1: nn.Linear, fc2: nn.Linear, *, eps: float, head_dim: int = 64, mask: Optional[torch.Tensor] = None, ls1=None, ls2=None) -> torch.Tensor:
+    """pre-LayerNorm transformer block (VideoMAE, DINOv2, CLIP / open_clip towers): x + [ls1 *] out_proj(attn(ln1(x))), then x + [ls2 *] fc2(gelu(fc1(ln2(x))));
+    every residual rides in a GEMM epilogue.  `qkv_w` / `qkv_b`: the fused [3D, D] projection (bf16); `mask`: the head_dim-64 kernel's byte mask;
+    `ls1` / `ls2`: LayerScale modules (`lambda1` [D]), applied through the AdaLN-gate epilogue with a constant gate."""
+    N, S, D = x.shape
+
+    def resid_linear(a, lin, ls, x):
+        if ls is None:
+            return ops.linear(a, bf16(lin.weight), bf16(lin.bias), epilogue=ops.EPI_RESID, resid=x)
+        g = bf16(ls.lambda1)
+        return ops.linear(a, bf16(lin.weight), bf16(lin.bias), epilogue=ops.EPI_GATE_RESID, resid=x, gate0=g, gate1=g, rows_per_batch=N * S, split=0, gate_stride=0)
+    h = ops.layernorm(x, bf16(ln1.weight), bf16(ln1.bias), eps)
+    qkv = ops.linear(h, qkv_w, qkv_b).view(N, S, 3, heads, head_dim)
+    if head_dim == 64:
+        a = ops.attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], mask=mask)
+    elif mask is None:
+        a = ops.attention_small(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2])
+    else:
+        raise NotImplementedError("masked attention at head_dim 64 only")
+    x = resid_linear(a, out_proj, ls1, x)
+    h = ops.layernorm(x, bf16(ln2.weight), bf16(ln2.bias), eps)
+    h = ops.linear(h, bf16(fc1.weight), bf16(fc1.bias), epilogue=ops.EPI_GELU_ERF)
+    return resid_linear(h, fc2, ls2, x)

@@ -14,11 +14,7 @@ import torch
 from torch import nn
 
 from . import ops
-
-
-def _b(t: torch.Tensor) -> torch.Tensor:
-    t = t.detach()
-    return t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)
+from .layers import bf16, prenorm_block
 
 
 class _MHA(nn.Module):
@@ -46,14 +42,8 @@ class ResidualAttentionBlock(nn.Module):
         self.mlp = _MLP(d, int(d * mlp_ratio))
 
     def forward(self, x: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
-        B, S, D = x.shape
-        h = ops.layernorm(x, _b(self.ln_1.weight), _b(self.ln_1.bias), self.ln_1.eps)
-        qkv = ops.linear(h, _b(self.attn.in_proj_weight), _b(self.attn.in_proj_bias)).view(B, S, 3, self.heads, 64)
-        a = ops.attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], mask=mask)
-        x = ops.linear(a, _b(self.attn.out_proj.weight), _b(self.attn.out_proj.bias), epilogue=ops.EPI_RESID, resid=x)
-        h = ops.layernorm(x, _b(self.ln_2.weight), _b(self.ln_2.bias), self.ln_2.eps)
-        h = ops.linear(h, _b(self.mlp.c_fc.weight), _b(self.mlp.c_fc.bias), epilogue=ops.EPI_GELU_ERF)
-        return ops.linear(h, _b(self.mlp.c_proj.weight), _b(self.mlp.c_proj.bias), epilogue=ops.EPI_RESID, resid=x)
+        return prenorm_block(x, self.heads, self.ln_1, bf16(self.attn.in_proj_weight), bf16(self.attn.in_proj_bias), self.attn.out_proj, self.ln_2, self.mlp.c_fc,
+                             self.mlp.c_proj, eps=self.ln_1.eps, mask=mask)
 
 
 class _Transformer(nn.Module):
@@ -125,14 +115,14 @@ class FrozenOpenCLIPEmbedder(nn.Module):
         if not text.is_cuda:
             raise ops.HipOnly("FrozenOpenCLIPEmbedder: token ids on the GPU expected")
         m = self.model
-        x = ops.add_rows(_b(m.token_embedding.weight)[text].contiguous(), _b(m.positional_embedding)[:text.shape[1]].contiguous())     # :221-222
+        x = ops.add_rows(bf16(m.token_embedding.weight)[text].contiguous(), bf16(m.positional_embedding)[:text.shape[1]].contiguous())     # :221-222
         mask = m.causal_mask(text.shape[1], text.device)
         blocks = m.transformer.resblocks
         for i, r in enumerate(blocks):                                                                                                      # :229-237
             if i == len(blocks) - self.layer_idx:
                 break
             x = r(x, mask)
-        return ops.layernorm(x, _b(m.ln_final.weight), _b(m.ln_final.bias), m.ln_final.eps)                                               # :226
+        return ops.layernorm(x, bf16(m.ln_final.weight), bf16(m.ln_final.bias), m.ln_final.eps)                                               # :226
 
     def encode(self, text):
         return self(text)

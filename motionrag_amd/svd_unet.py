@@ -22,16 +22,12 @@ from torch import nn
 
 from . import ops
 from .attn_processor import Attention
-from .dynamicrafter import _CACHE, TembBank, _cat0, conv3x3, conv_t3, temb_proj
+from .dynamicrafter import TembBank, temb_proj
+from .layers import CACHE, cat0, conv3x3, conv_t3, host_scalar
 
 
 def _ln(n: nn.LayerNorm, x):
     return ops.layernorm(x, n.weight, n.bias, n.eps)
-
-
-def _sigmoid_scalar(p: nn.Parameter) -> float:
-    """AlphaBlender's learned scalar, read back once per weight version (host sync only on the first call)"""
-    return _CACHE.get(("mix", id(p)), p, lambda: float(torch.sigmoid(p.detach().float()).item()))
 
 
 class TimestepEmbedding(nn.Module):
@@ -52,7 +48,7 @@ class AlphaBlender(nn.Module):
         self.mix_factor = nn.Parameter(torch.tensor([alpha]))
 
     def forward(self, x_spatial, x_temporal):
-        a = _sigmoid_scalar(self.mix_factor)
+        a = host_scalar(torch.sigmoid, self.mix_factor)
         return ops.axpby(x_spatial, x_temporal, a, 1.0 - a)
 
 
@@ -75,7 +71,7 @@ class ResnetBlock2D(nn.Module):
         co = h.shape[-1]
         h = ops.groupnorm(h.view(N, H * W, co), self.norm2.weight, self.norm2.bias, 32, self.norm2.eps, silu=True, emb=t).view(N, H, W, co)
         if self.conv_shortcut is not None:
-            w = _CACHE.get(("sc", id(self.conv_shortcut)), self.conv_shortcut.weight, lambda: self.conv_shortcut.weight.detach().reshape(co, C).contiguous())
+            w = CACHE.get(("sc", id(self.conv_shortcut)), self.conv_shortcut.weight, lambda: self.conv_shortcut.weight.detach().reshape(co, C).contiguous())
             x = ops.linear(x, w, self.conv_shortcut.bias)
         return conv3x3(h, self.conv2, resid=x)
 
@@ -116,7 +112,7 @@ class SpatioTemporalResBlock(nn.Module):
         N, H, W, C = s.shape
         # time_mixer(s, t) with t = s + c (the temporal block's residual form): a s + (1 - a)(s + c) = s + (1 - a) c -- the blend rides in the epilogue
         # of the temporal block's last convolution (one rounding of the mixed value instead of the package's three; no separate pass over the activation)
-        a = _sigmoid_scalar(self.time_mixer.mix_factor)
+        a = host_scalar(torch.sigmoid, self.time_mixer.mix_factor)
         return self.temporal_res_block(s.view(N, H * W, C), silu_temb, b, branch_scale=1.0 - a).view(N, H, W, C)
 
 
@@ -135,7 +131,7 @@ class AttnProcessor2_0:
         Nb, L, C = x.shape
         H = attn.heads
         if encoder_hidden_states is None:
-            w = _CACHE.get(("qkv", id(attn)), (attn.to_q.weight, attn.to_k.weight, attn.to_v.weight), lambda: _cat0([attn.to_q.weight, attn.to_k.weight, attn.to_v.weight]))
+            w = CACHE.get(("qkv", id(attn)), (attn.to_q.weight, attn.to_k.weight, attn.to_v.weight), lambda: cat0([attn.to_q.weight, attn.to_k.weight, attn.to_v.weight]))
             qkv = ops.linear(x, w)
             if temporal is None:
                 q5 = qkv.view(Nb, L, 3, H, 64)
@@ -150,7 +146,7 @@ class AttnProcessor2_0:
         else:
             ctx = encoder_hidden_states.contiguous()
             q = ops.linear(x, attn.to_q.weight).view(Nb, L, H, 64)
-            wkv = _CACHE.get(("kv", id(attn)), (attn.to_k.weight, attn.to_v.weight), lambda: _cat0([attn.to_k.weight, attn.to_v.weight]))
+            wkv = CACHE.get(("kv", id(attn)), (attn.to_k.weight, attn.to_v.weight), lambda: cat0([attn.to_k.weight, attn.to_v.weight]))
             kv = ops.linear(ctx, wkv)
             o = ops.attention(q, kv[..., :C].unflatten(-1, (H, 64)), kv[..., C:].unflatten(-1, (H, 64)), kv_batch_div=Nb // ctx.shape[0])
         if residual is not None:                                                        # block's `attn(norm(x)) + x` in the projection's epilogue
@@ -171,7 +167,7 @@ class FeedForward(nn.Module):
 
     def forward(self, x, resid=None):
         pj = self.net[0].proj
-        w, b = _CACHE.get(("geglu", id(pj)), (pj.weight, pj.bias), lambda: ops.geglu_interleave(pj.weight, pj.bias))
+        w, b = CACHE.get(("geglu", id(pj)), (pj.weight, pj.bias), lambda: ops.geglu_interleave(pj.weight, pj.bias))
         h = ops.linear(x, w, b, epilogue=ops.EPI_GEGLU)                             # value * gelu(gate) in the GEMM epilogue
         if resid is not None:
             return ops.linear(h, self.net[2].weight, self.net[2].bias, epilogue=ops.EPI_RESID, resid=resid)

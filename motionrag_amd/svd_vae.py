@@ -12,16 +12,15 @@ import torch
 from torch import nn
 
 from . import ops
-from .dynamicrafter import _CACHE, _lin_w, conv3x3, conv_t3
-from .dynamicrafter_vae import DiagonalGaussianDistribution, _b, _conv_small_cin
-from .svd_unet import _sigmoid_scalar
+from .dynamicrafter_vae import DiagonalGaussianDistribution
+from .layers import CACHE, _conv_small_cin, bf16, conv3x3, conv_t3, host_scalar, lin_w
 
 
 def _gn(x: torch.Tensor, gn: nn.GroupNorm, silu: bool, frames_per_sample: int = 1) -> torch.Tensor:
     """x [N, H, W, C]; statistics per image, or per clip over (t, h, w) when frames_per_sample > 1 (the temporal blocks' 5-D GroupNorm)"""
     N, H, W, C = x.shape
     f = frames_per_sample
-    return ops.groupnorm(x.view(N // f, f * H * W, C), _b(gn.weight), _b(gn.bias), gn.num_groups, gn.eps, silu=silu).view(N, H, W, C)
+    return ops.groupnorm(x.view(N // f, f * H * W, C), bf16(gn.weight), bf16(gn.bias), gn.num_groups, gn.eps, silu=silu).view(N, H, W, C)
 
 
 class ResnetBlock2D(nn.Module):
@@ -39,7 +38,7 @@ class ResnetBlock2D(nn.Module):
         h = conv3x3(_gn(x, self.norm1, True), self.conv1)
         h = _gn(h, self.norm2, True)
         if self.conv_shortcut is not None:
-            x = ops.linear(x, _b(_lin_w(self.conv_shortcut)), _b(self.conv_shortcut.bias))
+            x = ops.linear(x, bf16(lin_w(self.conv_shortcut)), bf16(self.conv_shortcut.bias))
         return conv3x3(h, self.conv2, resid=x)
 
 
@@ -79,7 +78,7 @@ class SpatioTemporalResBlock(nn.Module):
     def forward(self, x: torch.Tensor, num_frames: int) -> torch.Tensor:
         s = self.spatial_res_block(x)
         t = self.temporal_res_block(s, num_frames)
-        a = 1.0 - _sigmoid_scalar(self.time_mixer.mix_factor)
+        a = 1.0 - host_scalar(torch.sigmoid, self.time_mixer.mix_factor)
         return ops.axpby(s, t, a, 1.0 - a)
 
 
@@ -96,16 +95,16 @@ class Attention(nn.Module):
         N, H, W, C = x.shape
         S = H * W
         h = _gn(x, self.group_norm, False).view(N, S, C)
-        q = ops.linear(h, _b(self.to_q.weight), _b(self.to_q.bias))
-        k = ops.linear(h, _b(self.to_k.weight), _b(self.to_k.bias))
+        q = ops.linear(h, bf16(self.to_q.weight), bf16(self.to_q.bias))
+        k = ops.linear(h, bf16(self.to_k.weight), bf16(self.to_k.bias))
         a = torch.empty(N, S, C, dtype=torch.bfloat16, device=x.device)
         scores = torch.empty(S, S, dtype=torch.bfloat16, device=x.device)
         for n in range(N):
             ops.linear(q[n], k[n], out=scores)
             ops.softmax_rows(scores, scale=float(C) ** -0.5, out=scores)
-            vt = ops.linear(_b(self.to_v.weight), h[n])                                   # V^T = Wv h^T: no transpose pass; the bias rides below (rows of P sum to 1)
-            ops.linear(scores, vt, _b(self.to_v.bias), out=a[n])
-        return ops.linear(a, _b(self.to_out[0].weight), _b(self.to_out[0].bias), epilogue=ops.EPI_RESID, resid=x.view(N, S, C)).view(N, H, W, C)
+            vt = ops.linear(bf16(self.to_v.weight), h[n])                                   # V^T = Wv h^T: no transpose pass; the bias rides below (rows of P sum to 1)
+            ops.linear(scores, vt, bf16(self.to_v.bias), out=a[n])
+        return ops.linear(a, bf16(self.to_out[0].weight), bf16(self.to_out[0].bias), epilogue=ops.EPI_RESID, resid=x.view(N, S, C)).view(N, H, W, C)
 
 
 class _Sampler(nn.Module):
@@ -145,8 +144,8 @@ class Encoder(nn.Module):
             if hasattr(blk, "downsamplers"):
                 conv = blk.downsamplers[0].conv
                 C = h.shape[-1]
-                wk = _CACHE.get(("c3", id(conv)), conv.weight, lambda: _b(conv.weight).permute(0, 2, 3, 1).reshape(conv.weight.shape[0], 9 * C).contiguous())
-                h = ops.conv_implicit(h.contiguous(), wk, _b(conv.bias), ops.CONV_3X3, stride=2, asym_pad=True)          # F.pad(x, (0, 1, 0, 1)) + stride-2 conv
+                wk = CACHE.get(("c3", id(conv)), conv.weight, lambda: bf16(conv.weight).permute(0, 2, 3, 1).reshape(conv.weight.shape[0], 9 * C).contiguous())
+                h = ops.conv_implicit(h.contiguous(), wk, bf16(conv.bias), ops.CONV_3X3, stride=2, asym_pad=True)          # F.pad(x, (0, 1, 0, 1)) + stride-2 conv
         h = self.mid_block.resnets[0](h)
         h = self.mid_block.attentions[0](h)
         h = self.mid_block.resnets[1](h)
@@ -192,17 +191,17 @@ class TemporalDecoder(nn.Module):
 
         def build_out():                                                      # 3 output channels padded to 8: the temporal row gather moves 16-byte granules
             cin = conv.weight.shape[1]
-            w = torch.nn.functional.pad(_b(conv.weight).permute(0, 2, 3, 1).reshape(co, 9 * cin), (0, 0, 0, 8 - co))
-            return w.contiguous(), torch.nn.functional.pad(_b(conv.bias), (0, 8 - co)).contiguous()
-        wk, bk = _CACHE.get(("svdvae_out", id(conv)), (conv.weight, conv.bias), build_out)
+            w = torch.nn.functional.pad(bf16(conv.weight).permute(0, 2, 3, 1).reshape(co, 9 * cin), (0, 0, 0, 8 - co))
+            return w.contiguous(), torch.nn.functional.pad(bf16(conv.bias), (0, 8 - co)).contiguous()
+        wk, bk = CACHE.get(("svdvae_out", id(conv)), (conv.weight, conv.bias), build_out)
         y = ops.conv_implicit(h.contiguous(), wk, bk, ops.CONV_3X3)          # [(b f), H, W, 8]
         N, H, W, _ = y.shape
 
         def build_t():                                                        # Conv3d (3, 1, 1) over frames on the padded channels: [4, (kt, c8)] (ops.linear pads K = 24 to a K-tile)
-            w = torch.nn.functional.pad(_b(tconv.weight)[:, :, :, 0, 0], (0, 0, 0, 8 - co)).permute(0, 2, 1).reshape(co, 24)
+            w = torch.nn.functional.pad(bf16(tconv.weight)[:, :, :, 0, 0], (0, 0, 0, 8 - co)).permute(0, 2, 1).reshape(co, 24)
             w = torch.nn.functional.pad(w, (0, 0, 0, 4 - co))
-            return w.contiguous(), torch.nn.functional.pad(_b(tconv.bias), (0, 4 - co)).contiguous()
-        wt, bt = _CACHE.get(("svdvae_tout", id(tconv)), (tconv.weight, tconv.bias), build_t)
+            return w.contiguous(), torch.nn.functional.pad(bf16(tconv.bias), (0, 4 - co)).contiguous()
+        wt, bt = CACHE.get(("svdvae_tout", id(tconv)), (tconv.weight, tconv.bias), build_t)
         rows = ops.unfold_t3(y.view(N, H * W, 8), N // num_frames, num_frames)
         return ops.linear(rows, wt, bt).view(N, H, W, 4)[..., :co]
 
@@ -244,7 +243,7 @@ class AutoencoderKLTemporalDecoder(nn.Module):
         if not x.is_cuda:
             raise ops.HipOnly("AutoencoderKLTemporalDecoder.encode: GPU tensors only")
         h = self.encoder(x.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous())
-        moments = ops.linear(h, _b(_lin_w(self.quant_conv)), _b(self.quant_conv.bias)).permute(0, 3, 1, 2)
+        moments = ops.linear(h, bf16(lin_w(self.quant_conv)), bf16(self.quant_conv.bias)).permute(0, 3, 1, 2)
         return _EncodeOut(DiagonalGaussianDistribution(moments))
 
     @torch.no_grad()

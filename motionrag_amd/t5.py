@@ -23,12 +23,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .dynamicrafter import _CACHE
-
-
-def _b(t: torch.Tensor) -> torch.Tensor:
-    t = t.detach()
-    return t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)
+from .layers import CACHE, Holder, bf16
 
 
 class T5LayerNorm(nn.Module):
@@ -47,10 +42,6 @@ class _Attention(nn.Module):
             self.relative_attention_bias = nn.Embedding(num_buckets, heads)
 
 
-class _Holder(nn.Module):
-    pass
-
-
 class _FF(nn.Module):
     def __init__(self, d_model: int, d_ff: int):
         super().__init__()
@@ -60,7 +51,7 @@ class _FF(nn.Module):
 
 
 def _sublayer(inner: nn.Module, name: str, d_model: int, eps: float) -> nn.Module:
-    m = _Holder()
+    m = Holder()
     setattr(m, name, inner)
     m.layer_norm = T5LayerNorm(d_model, eps)
     return m
@@ -99,11 +90,11 @@ class T5EncoderModel(nn.Module):
         self.num_buckets, self.max_distance = relative_attention_num_buckets, relative_attention_max_distance
         inner = num_heads * d_kv
         self.shared = nn.Embedding(vocab_size, d_model)
-        self.encoder = _Holder()
+        self.encoder = Holder()
         self.encoder.embed_tokens = self.shared                                          # tied, as in transformers (both keys appear in the state dict)
         blocks = []
         for i in range(num_layers):
-            blk = _Holder()
+            blk = Holder()
             blk.layer = nn.ModuleList([_sublayer(_Attention(d_model, inner, num_heads, i == 0, relative_attention_num_buckets), "SelfAttention", d_model, layer_norm_epsilon),
                                        _sublayer(_FF(d_model, d_ff), "DenseReluDense", d_model, layer_norm_epsilon)])
             blocks.append(blk)
@@ -119,7 +110,7 @@ class T5EncoderModel(nn.Module):
             mem = torch.arange(S, device=device)[None, :]
             b = relative_position_bucket(mem - ctx, self.num_buckets, self.max_distance)
             return tab.detach().float()[b].permute(2, 0, 1).contiguous()
-        return _CACHE.get(("t5_bias", id(self), S), tab, build)
+        return CACHE.get(("t5_bias", id(self), S), tab, build)
 
     @torch.no_grad()
     def forward(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, **_unused) -> T5Output:
@@ -127,7 +118,7 @@ class T5EncoderModel(nn.Module):
             raise ops.HipOnly("T5EncoderModel: GPU tensors only")
         B, S = input_ids.shape
         H = self.heads
-        x = _b(self.shared.weight)[input_ids].contiguous()                               # embedding row gather (plumbing)
+        x = bf16(self.shared.weight)[input_ids].contiguous()                               # embedding row gather (plumbing)
         bias = self._position_bias(S, input_ids.device)
         biases = None
         if attention_mask is not None:                                                   # key-padding mask: folded into a per-sample copy of the bias
@@ -136,9 +127,9 @@ class T5EncoderModel(nn.Module):
         for blk in self.encoder.block:
             sa, ff = blk.layer[0], blk.layer[1]
             att, dn = sa.SelfAttention, ff.DenseReluDense
-            h = ops.layernorm(x, _b(sa.layer_norm.weight), None, sa.layer_norm.variance_epsilon, rms=True)
-            wqkv = _CACHE.get(("t5_qkv", id(att)), (att.q.weight, att.k.weight, att.v.weight),
-                              lambda: torch.cat([_b(att.q.weight), _b(att.k.weight), _b(att.v.weight)], 0).contiguous())
+            h = ops.layernorm(x, bf16(sa.layer_norm.weight), None, sa.layer_norm.variance_epsilon, rms=True)
+            wqkv = CACHE.get(("t5_qkv", id(att)), (att.q.weight, att.k.weight, att.v.weight),
+                              lambda: torch.cat([bf16(att.q.weight), bf16(att.k.weight), bf16(att.v.weight)], 0).contiguous())
             qkv = ops.linear(h, wqkv).view(B, S, 3, H, 64)
             if biases is None:
                 a = ops.attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], scale=1.0, bias=bias)
@@ -146,12 +137,12 @@ class T5EncoderModel(nn.Module):
                 a = torch.empty(B, S, H * 64, dtype=torch.bfloat16, device=x.device)
                 for b in range(B):
                     ops.attention(qkv[b:b + 1, :, 0], qkv[b:b + 1, :, 1], qkv[b:b + 1, :, 2], scale=1.0, bias=biases[b], out=a[b:b + 1])
-            x = ops.linear(a, _b(att.o.weight), epilogue=ops.EPI_RESID, resid=x)
-            h = ops.layernorm(x, _b(ff.layer_norm.weight), None, ff.layer_norm.variance_epsilon, rms=True)
+            x = ops.linear(a, bf16(att.o.weight), epilogue=ops.EPI_RESID, resid=x)
+            h = ops.layernorm(x, bf16(ff.layer_norm.weight), None, ff.layer_norm.variance_epsilon, rms=True)
             # hidden_gelu = gelu_new(wi_0 h), hidden_linear = wi_1 h, product: the GEGLU epilogue with value = wi_1, gate = wi_0
-            wg = _CACHE.get(("t5_geglu", id(dn)), (dn.wi_0.weight, dn.wi_1.weight),
-                            lambda: ops.geglu_interleave(torch.cat([_b(dn.wi_1.weight), _b(dn.wi_0.weight)], 0), None)[0])
+            wg = CACHE.get(("t5_geglu", id(dn)), (dn.wi_0.weight, dn.wi_1.weight),
+                            lambda: ops.geglu_interleave(torch.cat([bf16(dn.wi_1.weight), bf16(dn.wi_0.weight)], 0), None)[0])
             g = ops.linear(h, wg, epilogue=ops.EPI_GEGLU, geglu_tanh=True)
-            x = ops.linear(g, _b(dn.wo.weight), epilogue=ops.EPI_RESID, resid=x)
+            x = ops.linear(g, bf16(dn.wo.weight), epilogue=ops.EPI_RESID, resid=x)
         fl = self.encoder.final_layer_norm
-        return T5Output(ops.layernorm(x, _b(fl.weight), None, fl.variance_epsilon, rms=True))
+        return T5Output(ops.layernorm(x, bf16(fl.weight), None, fl.variance_epsilon, rms=True))

@@ -22,12 +22,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .dynamicrafter import _CACHE
-from .dynamicrafter_vae import _b
-
-
-class _Holder(nn.Module):
-    pass
+from .layers import CACHE, Holder, bf16
 
 
 class NewModel(nn.Module):
@@ -41,22 +36,22 @@ class NewModel(nn.Module):
         self.config = SimpleNamespace(vocab_size=vocab_size, hidden_size=hidden_size, num_hidden_layers=num_hidden_layers, num_attention_heads=num_attention_heads,
                                       intermediate_size=intermediate_size, layer_norm_eps=layer_norm_eps, max_position_embeddings=max_position_embeddings,
                                       rope_theta=rope_theta, rope_scaling_factor=rope_scaling_factor)
-        self.embeddings = _Holder()
+        self.embeddings = Holder()
         self.embeddings.word_embeddings = nn.Embedding(vocab_size, hidden_size, padding_idx=0)
         self.embeddings.LayerNorm = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
         layers = []
         for _ in range(num_hidden_layers):
-            lyr = _Holder()
-            lyr.attention = _Holder()
+            lyr = Holder()
+            lyr.attention = Holder()
             lyr.attention.qkv_proj = nn.Linear(hidden_size, 3 * hidden_size)
             lyr.attention.o_proj = nn.Linear(hidden_size, hidden_size)
             lyr.attn_ln = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
-            lyr.mlp = _Holder()
+            lyr.mlp = Holder()
             lyr.mlp.up_gate_proj = nn.Linear(hidden_size, 2 * intermediate_size, bias=False)
             lyr.mlp.down_proj = nn.Linear(intermediate_size, hidden_size)
             lyr.mlp_ln = nn.LayerNorm(hidden_size, eps=layer_norm_eps)
             layers.append(lyr)
-        self.encoder = _Holder()
+        self.encoder = Holder()
         self.encoder.layer = nn.ModuleList(layers)
         self._rope_cache: Dict = {}
 
@@ -82,8 +77,8 @@ class NewModel(nn.Module):
             per_head = torch.stack([torch.arange(32), torch.arange(32) + 32], dim=1).reshape(-1)                 # [0, 32, 1, 33, ...]
             qk = (torch.arange(heads)[:, None] * 64 + per_head[None, :]).reshape(-1)
             rows = torch.cat([qk, d + qk, 2 * d + torch.arange(d)]).to(lin.weight.device)
-            return _b(lin.weight)[rows].contiguous(), _b(lin.bias)[rows].contiguous()
-        return _CACHE.get(("gte_qkv", id(lin)), (lin.weight, lin.bias), build)
+            return bf16(lin.weight)[rows].contiguous(), bf16(lin.bias)[rows].contiguous()
+        return CACHE.get(("gte_qkv", id(lin)), (lin.weight, lin.bias), build)
 
     @torch.no_grad()
     def forward(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, **_unused):
@@ -96,19 +91,19 @@ class NewModel(nn.Module):
         B, S = input_ids.shape
         H, d = c.num_attention_heads, c.hidden_size
         emb = self.embeddings
-        x = ops.layernorm(_b(emb.word_embeddings.weight)[input_ids].contiguous(), _b(emb.LayerNorm.weight), _b(emb.LayerNorm.bias), c.layer_norm_eps)
+        x = ops.layernorm(bf16(emb.word_embeddings.weight)[input_ids].contiguous(), bf16(emb.LayerNorm.weight), bf16(emb.LayerNorm.bias), c.layer_norm_eps)
         cos, sin = self._rope(S, input_ids.device)
         for lyr in self.encoder.layer:
             att, mlp = lyr.attention, lyr.mlp
             wqkv, bqkv = self._qkv_interleaved(att.qkv_proj, H)
             qkv = ops.qkv_linear_qknorm_rope(x, wqkv, bqkv, H, None, None, None, None, cos, sin, 0).view(B, S, 3, H, 64)
             a = ops.attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2])
-            x = ops.linear(a, _b(att.o_proj.weight), _b(att.o_proj.bias), epilogue=ops.EPI_RESID, resid=x)
-            x = ops.layernorm(x, _b(lyr.attn_ln.weight), _b(lyr.attn_ln.bias), c.layer_norm_eps)
-            wg = _CACHE.get(("gte_geglu", id(mlp.up_gate_proj)), mlp.up_gate_proj.weight, lambda: ops.geglu_interleave(_b(mlp.up_gate_proj.weight), None)[0])
+            x = ops.linear(a, bf16(att.o_proj.weight), bf16(att.o_proj.bias), epilogue=ops.EPI_RESID, resid=x)
+            x = ops.layernorm(x, bf16(lyr.attn_ln.weight), bf16(lyr.attn_ln.bias), c.layer_norm_eps)
+            wg = CACHE.get(("gte_geglu", id(mlp.up_gate_proj)), mlp.up_gate_proj.weight, lambda: ops.geglu_interleave(bf16(mlp.up_gate_proj.weight), None)[0])
             g = ops.linear(x, wg, epilogue=ops.EPI_GEGLU)                                   # [up | gate] -> up * gelu_erf(gate)
-            x = ops.linear(g, _b(mlp.down_proj.weight), _b(mlp.down_proj.bias), epilogue=ops.EPI_RESID, resid=x)
-            x = ops.layernorm(x, _b(lyr.mlp_ln.weight), _b(lyr.mlp_ln.bias), c.layer_norm_eps)
+            x = ops.linear(g, bf16(mlp.down_proj.weight), bf16(mlp.down_proj.bias), epilogue=ops.EPI_RESID, resid=x)
+            x = ops.layernorm(x, bf16(lyr.mlp_ln.weight), bf16(lyr.mlp_ln.bias), c.layer_norm_eps)
         return _Output(x)
 
 
