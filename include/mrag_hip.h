@@ -711,6 +711,19 @@ int mrag_geglu_bf16(void* stream, const void* x, void* y, int64_t rows, int64_t 
 int mrag_ddim_v_step_f32(void* stream, const void* v_pred, float* x, const float* noise, int64_t n, float guidance,
                          float sqrt_alpha_t, float sqrt_one_minus_alpha_t, float rescale, float sqrt_alpha_prev,
                          float dir_coef, float sigma);
+/* The same step with guidance rescale (samplers/ddim.py:244-247, utils_diffusion.py:148-159 rescale_noise_cfg), per sample s:
+ *   g = v_u + guidance (v_c - v_u);  r_s = std(v_c[s]) / std(g[s])  (unbiased, over the sample's n_per_sample elements);
+ *   v = guidance_rescale (g r_s) + (1 - guidance_rescale) g;  then the update above.  All arithmetic fp32.
+ * v_pred bf16 [2 batch, n_per_sample] (cond FIRST); x, noise fp32 [batch, n_per_sample]; noise NULL = 0.
+ * Two launches on `stream` (partial statistics into `workspace`, then fold + update); nothing is allocated, synchronised or read
+ * back, no workgroup waits for another, and the result is bit-identical from run to run.  std(g) == 0 is not special-cased.
+ * MRAG_EINVAL: null pointer, batch < 1, n_per_sample < 2, guidance_rescale outside (0, 1], workspace smaller than
+ * mrag_ddim_v_rescale_workspace_bytes(batch, n_per_sample) or not 16-byte aligned.                                            */
+int64_t mrag_ddim_v_rescale_workspace_bytes(int64_t batch, int64_t n_per_sample);
+int mrag_ddim_v_step_rescaled_f32(void* stream, const void* v_pred, float* x, const float* noise, int64_t batch, int64_t n_per_sample,
+                                  float guidance, float guidance_rescale, float sqrt_alpha_t, float sqrt_one_minus_alpha_t,
+                                  float rescale, float sqrt_alpha_prev, float dir_coef, float sigma, void* workspace,
+                                  int64_t workspace_bytes);
 
 /* ------------------------------------------------------------------------ */
 /* Multi-GPU exchange step: RCCL all-gather over xGMI on a    */

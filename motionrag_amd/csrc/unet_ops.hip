@@ -10,6 +10,7 @@
 //   mrag_unfold_t3_bf16   row gather for nn.Conv3d (3,1,1), pad (1,0,0) (openaimodel3d.py:256-268)
 //   mrag_geglu_bf16       x * gelu(gate) (attention.py:448-455)
 //   mrag_ddim_v_step_f32  CFG + v-prediction DDIM update with dynamic rescale and eta noise (samplers/ddim.py:236-296)
+//   mrag_ddim_v_step_rescaled_f32  the same update behind guidance rescale (utils_diffusion.py:148-159): per-sample std reduction + update, two launches
 #include "common.h"
 #include "../../include/mrag_hip.h"
 
@@ -362,15 +363,120 @@ __global__ __launch_bounds__(256) void geglu_kernel(const bf16_t* x, bf16_t* y, 
 
 // samplers/ddim.py:236-296 (v-parameterisation):  v = v_u + s (v_c - v_u)   [cond FIRST in the batch, :219-237]
 //   eps = sa v + sb x ; x0 = (sa x - sb v) * rescale ; x <- sqrt(a_prev) x0 + dir eps + sigma noise
+// The two DDIM kernels share these.  Every fused multiply-add is spelled out and contraction is off, so that both kernels round alike whatever the
+// optimiser makes of the code around the call (left to -ffp-contract=fast, the vectoriser pairs the products differently from kernel to kernel and the
+// fused operations move with them).  The grouping is part of mrag_ddim_v_step_f32's contract: its results are compared bit for bit from build to build.
+__device__ __forceinline__ float cfg_mix(float vc, float vu, float s) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(s, vc - vu, vu);
+}
+
+// the new x[i] from the guided prediction v
+__device__ __forceinline__ float ddim_v_update(float v, float xx, const float* noise, long long i, float sa, float sb, float rescale, float sqrt_aprev,
+                                               float dir, float sigma) {
+#pragma clang fp contract(off)
+  const float eps = __builtin_fmaf(sb, xx, sa * v);
+  const float x0 = __builtin_fmaf(sa, xx, -(sb * v)) * rescale;
+  const float nz = noise ? sigma * noise[i] : 0.f;
+  return __builtin_fmaf(dir, eps, sqrt_aprev * x0) + nz;
+}
+
 __global__ __launch_bounds__(256) void ddim_v_kernel(const bf16_t* v_pred, float* x, const float* noise, long long n, float s, float sa, float sb,
                                                      float rescale, float sqrt_aprev, float dir, float sigma) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const float vc = bf2f(v_pred[i]), vu = bf2f(v_pred[n + i]);
-    const float v = vu + s * (vc - vu);
-    const float xx = x[i];
-    const float eps = sa * v + sb * xx;
-    const float x0 = (sa * xx - sb * v) * rescale;
-    x[i] = sqrt_aprev * x0 + dir * eps + (noise ? sigma * noise[i] : 0.f);
+    const float v = cfg_mix(bf2f(v_pred[i]), bf2f(v_pred[n + i]), s);
+    x[i] = ddim_v_update(v, x[i], noise, i, sa, sb, rescale, sqrt_aprev, dir, sigma);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- guidance rescale
+// utils_diffusion.py:148-159 rescale_noise_cfg in front of the update above: per sample, r = std(v_c) / std(g) over all n elements (unbiased), g the guided
+// prediction; v = phi (g r) + (1 - phi) g.  Two launches: partial statistics of P slices per sample, then every workgroup of the update folds its sample's
+// P partials in the same fixed order -- no workgroup waits for another, and nothing depends on arrival order.
+//
+// Statistics are (count, mean, M2 = sum (x - mean)^2) triples merged pairwise (Chan et al.); a thread gathers its own few elements as sums shifted by its
+// first element.  The count is shared by the two series, so a partial is 5 floats (padded to 8: one 32-byte record).
+struct RsStat { float n, mean_c, m2_c, mean_g, m2_g; };
+constexpr int RS_MAX_PARTS = 256, RS_RECORD_FLOATS = 8, RS_SLICE = 1024;
+
+inline int rs_parts(long long n) {
+  const long long p = (n + RS_SLICE - 1) / RS_SLICE;
+  return (int)(p < 1 ? 1 : p > RS_MAX_PARTS ? RS_MAX_PARTS : p);
+}
+
+__device__ __forceinline__ RsStat rs_merge(const RsStat a, const RsStat b) {
+  RsStat r;
+  r.n = a.n + b.n;
+  const float wb = r.n > 0.f ? b.n / r.n : 0.f, wab = a.n * wb;        // nb / n ; na nb / n
+  const float dc = b.mean_c - a.mean_c, dg = b.mean_g - a.mean_g;
+  r.mean_c = a.mean_c + dc * wb; r.m2_c = a.m2_c + b.m2_c + dc * dc * wab;
+  r.mean_g = a.mean_g + dg * wb; r.m2_g = a.m2_g + b.m2_g + dg * dg * wab;
+  return r;
+}
+
+// merge the 256 threads' triples in one fixed tree (lanes by halving distance, then the four waves in order); the result is valid in every thread
+__device__ __forceinline__ RsStat rs_block_merge(RsStat v, RsStat* lds /* [5] */) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    RsStat o;
+    o.n = __shfl_down(v.n, d, 64); o.mean_c = __shfl_down(v.mean_c, d, 64); o.m2_c = __shfl_down(v.m2_c, d, 64);
+    o.mean_g = __shfl_down(v.mean_g, d, 64); o.m2_g = __shfl_down(v.m2_g, d, 64);
+    v = rs_merge(v, o);                                                   // (what lanes >= 64 - d merge here is never read)
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) lds[wave] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) lds[4] = rs_merge(rs_merge(lds[0], lds[1]), rs_merge(lds[2], lds[3]));
+  __syncthreads();
+  return lds[4];
+}
+
+// grid (P, batch): workgroup (p, s) reduces elements [p L, (p + 1) L) of sample s, L = ceil(n / P)
+__global__ __launch_bounds__(256) void ddim_rescale_stats_kernel(const bf16_t* v_pred, float* part, long long n, long long total, float s) {
+  __shared__ RsStat lds[5];
+  const int P = gridDim.x;
+  const long long L = (n + P - 1) / P, i0 = blockIdx.x * L, i1 = i0 + L < n ? i0 + L : n;
+  const bf16_t* vc = v_pred + blockIdx.y * n;
+  const bf16_t* vu = vc + total;
+  float cnt = 0.f, kc = 0.f, kg = 0.f, s1c = 0.f, s2c = 0.f, s1g = 0.f, s2g = 0.f;
+  for (long long i = i0 + threadIdx.x; i < i1; i += 256) {
+    const float c = bf2f(vc[i]), g = cfg_mix(c, bf2f(vu[i]), s);
+    if (cnt == 0.f) { kc = c; kg = g; }                                   // the thread's pivot: its first element
+    const float dc = c - kc, dg = g - kg;
+    cnt += 1.f; s1c += dc; s2c += dc * dc; s1g += dg; s2g += dg * dg;
+  }
+  RsStat v{cnt, kc, 0.f, kg, 0.f};
+  if (cnt > 0.f) {
+    const float inv = 1.f / cnt;
+    v.mean_c = kc + s1c * inv; v.m2_c = fmaxf(s2c - s1c * s1c * inv, 0.f);
+    v.mean_g = kg + s1g * inv; v.m2_g = fmaxf(s2g - s1g * s1g * inv, 0.f);
+  }
+  v = rs_block_merge(v, lds);
+  if (threadIdx.x == 0) {
+    float* o = part + ((long long)blockIdx.y * P + blockIdx.x) * RS_RECORD_FLOATS;
+    o[0] = v.n; o[1] = v.mean_c; o[2] = v.m2_c; o[3] = v.mean_g; o[4] = v.m2_g;
+  }
+}
+
+// grid (Q, batch): fold the sample's P (<= 256: one per thread) partials, then update the workgroup's elements of that sample
+__global__ __launch_bounds__(256) void ddim_rescale_update_kernel(const bf16_t* v_pred, float* x, const float* noise, const float* part, int P, long long n,
+                                                                  long long total, float s, float phi, float sa, float sb, float rescale, float sqrt_aprev,
+                                                                  float dir, float sigma) {
+  __shared__ RsStat lds[5];
+  RsStat v{0.f, 0.f, 0.f, 0.f, 0.f};
+  if ((int)threadIdx.x < P) {
+    const float* o = part + ((long long)blockIdx.y * P + threadIdx.x) * RS_RECORD_FLOATS;
+    v = RsStat{o[0], o[1], o[2], o[3], o[4]};
+  }
+  v = rs_block_merge(v, lds);
+  const float nm1 = (float)(n - 1);
+  const float r = sqrtf(v.m2_c / nm1) / sqrtf(v.m2_g / nm1);             // std(g) == 0 is not special-cased: IEEE division, as the reference's
+  const float one_minus_phi = 1.f - phi;
+  const long long base = blockIdx.y * n;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const float g = cfg_mix(bf2f(v_pred[base + i]), bf2f(v_pred[total + base + i]), s);
+    const float vv = phi * (g * r) + one_minus_phi * g;
+    x[base + i] = ddim_v_update(vv, x[base + i], noise, base + i, sa, sb, rescale, sqrt_aprev, dir, sigma);
   }
 }
 
@@ -487,6 +593,32 @@ extern "C" int mrag_ddim_v_step_f32(void* stream, const void* v_pred, float* x, 
   if (!v_pred || !x || n <= 0) return MRAG_EINVAL;
   MRAG_LAUNCH(ddim_v_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)v_pred, x, noise, (long long)n, guidance,
               sqrt_alpha_t, sqrt_one_minus_alpha_t, rescale, sqrt_alpha_prev, dir_coef, sigma);
+  MRAG_LAUNCH_CHECK();
+  return MRAG_OK;
+}
+
+extern "C" int64_t mrag_ddim_v_rescale_workspace_bytes(int64_t batch, int64_t n_per_sample) {
+  if (batch < 1 || n_per_sample < 2) return 0;
+  return batch * rs_parts(n_per_sample) * RS_RECORD_FLOATS * (int64_t)sizeof(float);
+}
+
+extern "C" int mrag_ddim_v_step_rescaled_f32(void* stream, const void* v_pred, float* x, const float* noise, int64_t batch, int64_t n_per_sample,
+                                             float guidance, float guidance_rescale, float sqrt_alpha_t, float sqrt_one_minus_alpha_t, float rescale,
+                                             float sqrt_alpha_prev, float dir_coef, float sigma, void* workspace, int64_t workspace_bytes) {
+  if (!v_pred || !x || !workspace || batch < 1 || n_per_sample < 2) return MRAG_EINVAL;
+  if (!(guidance_rescale > 0.f && guidance_rescale <= 1.f)) return MRAG_EINVAL;
+  if (((uintptr_t)workspace & 15) || workspace_bytes < mrag_ddim_v_rescale_workspace_bytes(batch, n_per_sample)) return MRAG_EINVAL;
+  if (batch > 65535) return MRAG_ENOTSUP;                                   // grid.y
+  const long long n = n_per_sample, total = (long long)batch * n;
+  const int P = rs_parts(n);
+  long long q = (n + 1023) / 1024;                                          // >= 4 elements per thread
+  const long long cap = 4096 / batch > 16 ? 4096 / batch : 16;
+  if (q > cap) q = cap;
+  hipStream_t s = (hipStream_t)stream;
+  MRAG_LAUNCH(ddim_rescale_stats_kernel, dim3((unsigned)P, (unsigned)batch), dim3(256), 0, s, (const bf16_t*)v_pred, (float*)workspace, n, total, guidance);
+  MRAG_LAUNCH_CHECK();
+  MRAG_LAUNCH(ddim_rescale_update_kernel, dim3((unsigned)q, (unsigned)batch), dim3(256), 0, s, (const bf16_t*)v_pred, x, noise, (const float*)workspace, P, n,
+              total, guidance, guidance_rescale, sqrt_alpha_t, sqrt_one_minus_alpha_t, rescale, sqrt_alpha_prev, dir_coef, sigma);
   MRAG_LAUNCH_CHECK();
   return MRAG_OK;
 }

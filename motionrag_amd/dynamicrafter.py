@@ -502,9 +502,15 @@ class DDIMSampler:
         self.use_dynamic_rescale = use_dynamic_rescale
         self.scale_arr = np.concatenate((np.linspace(1.0, base_scale, turning_step), np.full(n, base_scale))).astype(np.float32)   # ddpm3d.py:535-541
 
-    def make_schedule(self, ddim_num_steps: int, ddim_eta: float = 0.0):
+    def make_schedule(self, ddim_num_steps: int, ddim_eta: float = 0.0, ddim_discretize: str = "uniform"):
         n = len(self.ac)
-        self.ddim_timesteps = np.asarray(list(range(0, n, n // ddim_num_steps))) + 1                  # utils_diffusion.py:57-60,71 ('uniform')
+        if ddim_discretize == "uniform":
+            self.ddim_timesteps = np.asarray(list(range(0, n, n // ddim_num_steps))) + 1              # utils_diffusion.py:57-60
+        elif ddim_discretize == "uniform_trailing":                                                   # :61-64: ends on t = n - 1 (zero terminal SNR)
+            self.ddim_timesteps = np.flip(np.round(np.arange(n, 0, -n / ddim_num_steps))).astype(np.int64) - 1
+        else:
+            raise NotImplementedError(f"ddim_discretize {ddim_discretize!r}: 'uniform' and 'uniform_trailing' are built ('quad' repeats timesteps; "
+                                      "no shipped config uses it)")
         a = self.ac32[self.ddim_timesteps]
         a_prev = np.asarray([self.ac32[0]] + self.ac32[self.ddim_timesteps[:-1]].tolist(), dtype=np.float32)
         self.ddim_alphas, self.ddim_alphas_prev = a, a_prev
@@ -522,17 +528,23 @@ class DDIMSampler:
 
     @torch.no_grad()
     def sample(self, model, x_T: torch.Tensor, cond, uncond, S: int, eta: float = 1.0, unconditional_guidance_scale: float = 2.0,
-               noises: Optional[List[torch.Tensor]] = None, callback=None) -> torch.Tensor:
-        """ddim_sampling (:135-200) + p_sample_ddim (:203-298); x_T fp32 latents [b, 4, t, h, w] (updated in place)."""
-        self.make_schedule(S, eta)
+               noises: Optional[List[torch.Tensor]] = None, callback=None, timestep_spacing: str = "uniform", guidance_rescale: float = 0.0) -> torch.Tensor:
+        """ddim_sampling (:135-200) + p_sample_ddim (:203-298); x_T fp32 latents [b, 4, t, h, w] (updated in place).  `guidance_rescale` > 0 (:246-247)
+        runs every update on the reduction + update kernel pair of `ops.ddim_v_step_rescaled_`."""
+        if not 0.0 <= guidance_rescale <= 1.0:
+            raise ValueError(f"guidance_rescale {guidance_rescale}: [0, 1] expected")
+        self.make_schedule(S, eta, timestep_spacing)
         x = x_T.to(torch.float32).contiguous()
         n_steps = len(self.ddim_timesteps)
         for i in range(n_steps):
             index = n_steps - 1 - i
             t, sa, sb, rescale, sqrt_aprev, dir_coef, sigma = self.step_coeffs(index)
             v = model(x, t, cond, uncond)
-            ops.ddim_v_step_(v.contiguous(), x, noises[i] if noises is not None else None, unconditional_guidance_scale, sa, sb, rescale,
-                             sqrt_aprev, dir_coef, sigma)
+            noise = noises[i] if noises is not None else None
+            if guidance_rescale > 0.0:
+                ops.ddim_v_step_rescaled_(v.contiguous(), x, noise, unconditional_guidance_scale, guidance_rescale, sa, sb, rescale, sqrt_aprev, dir_coef, sigma)
+            else:
+                ops.ddim_v_step_(v.contiguous(), x, noise, unconditional_guidance_scale, sa, sb, rescale, sqrt_aprev, dir_coef, sigma)
             if callback is not None:
                 callback(i, t, x)
         return x

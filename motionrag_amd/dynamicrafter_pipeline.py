@@ -8,7 +8,8 @@ with the same names, arguments and return layout.  `model` is the reference's La
 `encode_first_stage`, `decode_first_stage`, `uncond_type`, `model.conditioning_key` and `model.diffusion_model` from it.  The
 third-party pieces (OpenCLIP embedder, text encoder, first-stage VAE) stay whatever the caller supplies (SURVEY 8f "next" rows);
 `model.model.diffusion_model` must be `motionrag_amd.dynamicrafter.UNetModel`, the sampler is `motionrag_amd.dynamicrafter.DDIMSampler`
-(tables on the host, every update a gfx950 kernel).
+(tables on the host, every update a gfx950 kernel).  `timestep_spacing` 'uniform' / 'uniform_trailing', `guidance_rescale` and the `loop` / `interp`
+conditioning follow the reference; `multiple_cond_cfg`, the no-CFG path and 'quad' spacing are refused.
 
 One deliberate difference, forced by SURVEY Appendix D.3: the reference draws x_T and the per-step eta-noise with `torch.randn(..., device)`,
 whose stream differs between devices; here they come from a CPU generator (`seed`) or from the caller (`x_T`, `noises`) and are
@@ -38,9 +39,11 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
                            cfg_img=None, fs=None, text_input=False, multiple_cond_cfg=False, loop=False, interp=False,
                            timestep_spacing="uniform", guidance_rescale=0.0, ref_videos=None, ref_fusion_type=None, metadata: dict = None,
                            x_T: Optional[torch.Tensor] = None, noises: Optional[List[torch.Tensor]] = None, seed: int = 0, **kwargs):
-    if multiple_cond_cfg or loop or interp or guidance_rescale != 0.0 or timestep_spacing != "uniform":
-        raise NotImplementedError("the shipped pipeline calls with multiple_cond_cfg=False, loop=False, interp=False, guidance_rescale=0, 'uniform' "
-                                  "(pipelines/pipeline.py:96-115, configs/dynamicrafter/MotionRAG_open.yml:165-171)")
+    if multiple_cond_cfg:
+        raise NotImplementedError("multiple_cond_cfg (the three-branch guidance with cfg_img) is not built; the shipped pipeline calls with "
+                                  "multiple_cond_cfg=False (pipelines/pipeline.py:96-115, configs/dynamicrafter/MotionRAG_open.yml:165-171)")
+    if timestep_spacing not in ("uniform", "uniform_trailing"):
+        raise NotImplementedError(f"timestep_spacing {timestep_spacing!r}: 'uniform' and 'uniform_trailing' are built")
     if unconditional_guidance_scale == 1.0:
         raise NotImplementedError("classifier-free guidance is always on in the shipped configs (unconditional_guidance_scale 2.0)")
     device = videos.device
@@ -82,7 +85,11 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
     if model.model.conditioning_key != "hybrid":
         raise NotImplementedError("DynamiCrafter runs conditioning_key='hybrid'")
     z = get_latent_z(model, videos)                                                               # :229  b c t h w
-    img_cat_cond = z[:, :, :1].expand(-1, -1, z.shape[2], -1, -1)                                  # :235-236
+    if loop or interp:                                                                            # :230-233: first and last frame, zeros between
+        img_cat_cond = torch.zeros_like(z)
+        img_cat_cond[:, :, 0], img_cat_cond[:, :, -1] = z[:, :, 0], z[:, :, -1]
+    else:
+        img_cat_cond = z[:, :, :1].expand(-1, -1, z.shape[2], -1, -1)                              # :235-236
     cond["c_concat"] = [bf(img_cat_cond)]
 
     uc = {"c_crossattn": {}}                                                                       # :239-262
@@ -104,7 +111,7 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
 
     sampler = DDIMSampler(getattr(model, "alphas_cumprod_np", None), use_dynamic_rescale=getattr(model, "use_dynamic_rescale", True))
     denoiser = DynamiCrafterDenoiser(model.model.diffusion_model)
-    sampler.make_schedule(ddim_steps, ddim_eta)
+    sampler.make_schedule(ddim_steps, ddim_eta, timestep_spacing)
     n_steps = len(sampler.ddim_timesteps)
     batch_variants = []
     g = torch.Generator().manual_seed(seed)
@@ -112,7 +119,8 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
         xt = (torch.randn(tuple(noise_shape), generator=g) if x_T is None else x_T).to(device=device, dtype=torch.float32)
         ns = noises if noises is not None else [torch.randn(tuple(noise_shape), generator=g) for _ in range(n_steps)]
         ns = [n.to(device=device, dtype=torch.float32).contiguous() for n in ns]
-        samples = sampler.sample(denoiser, xt, cond, uc, S=ddim_steps, eta=ddim_eta, unconditional_guidance_scale=unconditional_guidance_scale, noises=ns)
+        samples = sampler.sample(denoiser, xt, cond, uc, S=ddim_steps, eta=ddim_eta, unconditional_guidance_scale=unconditional_guidance_scale, noises=ns,
+                                 timestep_spacing=timestep_spacing, guidance_rescale=guidance_rescale)
         batch_variants.append(model.decode_first_stage(samples))
     return torch.stack(batch_variants).permute(1, 0, 2, 3, 4, 5)                                    # variants, b, c, t, h, w -> b, variants, ...
 

@@ -973,3 +973,28 @@ def ddim_v_step_(v_pred: torch.Tensor, x: torch.Tensor, noise: Optional[torch.Te
     check(_lib.lib().mrag_ddim_v_step_f32(_stream(), _p(v_pred), _p(x), _p(noise), n, guidance, sqrt_alpha_t, sqrt_one_minus_alpha_t, rescale,
                                           sqrt_alpha_prev, dir_coef, sigma), "mrag_ddim_v_step_f32")
     return x
+
+
+def ddim_v_step_rescaled_(v_pred: torch.Tensor, x: torch.Tensor, noise: Optional[torch.Tensor], guidance: float, guidance_rescale: float,
+                          sqrt_alpha_t: float, sqrt_one_minus_alpha_t: float, rescale: float, sqrt_alpha_prev: float, dir_coef: float,
+                          sigma: float) -> torch.Tensor:
+    """`ddim_v_step_` with guidance rescale (0 < guidance_rescale <= 1): the guided prediction of each sample is scaled towards the standard deviation of
+    its conditional half before the update.  x fp32 [b, ...] (in place); v_pred bf16 [2b, ...], contiguous, the conditional half FIRST."""
+    _dev(v_pred, name="v_pred"); _dev(x, torch.float32, "x")
+    if noise is not None:
+        _dev(noise, torch.float32, "noise")
+    if x.dim() < 2 or v_pred.dim() != x.dim() or v_pred.shape[0] != 2 * x.shape[0] or v_pred.shape[1:] != x.shape[1:]:
+        raise ValueError("ddim_v_step_rescaled_: x must be [b, ...] and v_pred [2b, ...] of the same sample shape")
+    if not v_pred.is_contiguous() or not x.is_contiguous() or (noise is not None and (noise.shape != x.shape or not noise.is_contiguous())):
+        raise ValueError("ddim_v_step_rescaled_: v_pred, x and noise must be contiguous, noise of x's shape")
+    b = x.shape[0]
+    n = x.numel() // b
+    L = _lib.lib()
+    need = L.mrag_ddim_v_rescale_workspace_bytes(b, n)
+    if need <= 0:
+        raise ValueError("ddim_v_step_rescaled_: at least one sample of at least two elements required")
+    ws = _attn_workspace(x.device, need, "ddim_rescale")                  # grow-only per (device, stream): no allocation per step
+    check(L.mrag_ddim_v_step_rescaled_f32(_stream(), _p(v_pred), _p(x), _p(noise), b, n, guidance, guidance_rescale, sqrt_alpha_t,
+                                          sqrt_one_minus_alpha_t, rescale, sqrt_alpha_prev, dir_coef, sigma, _p(ws), ws.numel()),
+          "mrag_ddim_v_step_rescaled_f32")
+    return x
