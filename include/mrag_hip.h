@@ -699,6 +699,34 @@ typedef struct mrag_conv_args {
   float acc_scale;                 /* MRAG_EPI_RESID: y = resid + acc_scale * (conv + bias); 0 means 1                                          */
 } mrag_conv_args;
 int mrag_conv_bf16(void* stream, const mrag_conv_args* args);
+/* fp8 (OCP e4m3fn) 3x3 convolution -- OPT-IN (layers.set_conv_precision), beside the fp8 linears: nn.Conv2d(Cin, Cout, 3, stride 1, padding 1) on
+ * channels-last activations as an implicit GEMM on the block-scaled e4m3 MFMA.
+ *   y[n, ho, wo, co] = epilogue( 2^-w_exp[co] * sum_{ky, kx, ci} 2^-x_exp[pixel(n, ho + ky - 1, wo + kx - 1)] * x8[n, ho + ky - 1, wo + kx - 1, ci]
+ *                                                                * W8[co, (ky, kx, ci)] + bias[co] )
+ * (x8, x_exp) = mrag_quant_rows_e4m3 over the N H Wd pixel rows of Cin channels: one exponent per INPUT pixel, applied inside the MFMA per 64-channel
+ * step of one tap (exact); (W8, w_exp) the same quantiser over the [Cout, 9 Cin] tap-major weight: one exponent per output channel.  Pixels outside
+ * the image contribute zero.  fp32 accumulation in ascending (tap, channel) steps of 64.  Epilogues MRAG_EPI_NONE and MRAG_EPI_RESID with the
+ * rounding points of mrag_gemm_fp8 (conv + bias rounded to bf16, then the residual added and rounded); y may alias resid.
+ * MRAG_ENOTSUP -- the caller stays on mrag_conv_bf16 -- for stride != 1, upsample, asym_pad, t_taps (each must be 0 / 1 as named), any other epilogue,
+ * Cin % 64 != 0, Cout % 4 != 0, Cout <= 8 (the convolutions to 4 or 8 channels that write a model's output), H or Wd above 32 767, N H Wd above 2^31 - 1, and past the 32-bit source offsets: (255 / (H Wd) + 2) H Wd Cin bytes
+ * of activation below 2^31, 9 Cin Cout bytes of weight below 2^32.  MRAG_EINVAL for null or misaligned pointers (x8 / W8 16 bytes, y / resid /
+ * bias 8 bytes, the exponents 4) and non-positive sizes.  One tile shape (256 x 256) at every size.                                           */
+typedef struct mrag_conv_fp8_args {
+  const void* x8;            /* [N, H, Wd, Cin] e4m3fn bytes                     */
+  const void* W8;            /* [Cout, 9 Cin] e4m3fn bytes, (ky, kx, cin) order  */
+  const int32_t* x_exp;      /* [N H Wd]                                         */
+  const int32_t* w_exp;      /* [Cout]                                           */
+  const void* bias;          /* [Cout] bf16 or NULL                              */
+  void* y;                   /* [N, H, Wd, Cout] bf16                            */
+  const void* resid;         /* MRAG_EPI_RESID: the shape of y                   */
+  int32_t N, H, Wd, Cin, Cout;
+  int32_t stride, upsample, asym_pad, t_taps;   /* as in mrag_conv_args: 1, 0, 0, 0 or MRAG_ENOTSUP */
+  int32_t epilogue;          /* MRAG_EPI_NONE or MRAG_EPI_RESID                  */
+} mrag_conv_fp8_args;
+int mrag_conv_fp8(void* stream, const mrag_conv_fp8_args* args);
+/* host-side relaxed launch counter of mrag_conv_fp8 (slot 0), in the form of mrag_fp8_launch_counts: copies min(n, 1) slots into out_host (HOST
+ * memory) and returns 1.  Tests prove with it which kernel ran.                                                                                */
+int mrag_conv_fp8_launch_counts(uint64_t* out_host, int32_t n);
 /* row gather for nn.Conv3d((3,1,1), padding (1,0,0)), openaimodel3d.py:256-268:
  * dst[(b,t,hw), (kt,c)] = src[b, t+kt-1, hw, c]                                */
 int mrag_unfold_t3_bf16(void* stream, const void* src, void* dst, int32_t B, int32_t T, int64_t HW, int32_t C);

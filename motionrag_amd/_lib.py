@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libmrag_hip.so")
 # compiled in this order, at most MAX_COMPILERS at a time: the long units first, so that none of them starts late behind the short ones
-SOURCES = ["gemm_tiled.hip", "gemm_w4.hip", "topk_scan.hip", "gemm_conv.hip", "attn16.hip", "topk_dense.hip", "topk_mfma.hip", "attn_flash.hip", "gemm_skinny.hip", "gemm_fp8.hip", "api.hip", "gemm_bf16.hip", "gemm_k320.hip", "attn_fp8.hip",
+SOURCES = ["gemm_tiled.hip", "gemm_w4.hip", "topk_scan.hip", "gemm_conv.hip", "attn16.hip", "topk_dense.hip", "topk_mfma.hip", "attn_flash.hip", "gemm_skinny.hip", "gemm_fp8.hip", "conv_fp8.hip", "api.hip", "gemm_bf16.hip", "gemm_k320.hip", "attn_fp8.hip",
            "comm.hip", "norm.hip", "pointwise.hip", "preprocess.hip", "unet_ops.hip", "cama_seq.hip", "attn_small.hip", "topk.hip", "probe.hip"]
 MAX_COMPILERS = 16
 ABI_VERSION = 11
@@ -36,7 +36,7 @@ SYMBOLS = [
     "mrag_comm_unique_id", "mrag_comm_init", "mrag_comm_destroy", "mrag_allgather",
     "mrag_resize_patchify_bf16", "mrag_assemble_tokens_bf16", "mrag_softmax_rows_bf16", "mrag_denormalize_u8", "mrag_attn_small_bf16", "mrag_blend_tile_bf16", "mrag_cfg_dpm_step_bf16",
     "mrag_resampler_workspace_bytes", "mrag_resampler_fwd", "mrag_cama_encoder_workspace_bytes", "mrag_cama_encoder_fwd",
-    "mrag_quant_rows_e4m3", "mrag_gemm_fp8", "mrag_fp8_launch_counts",
+    "mrag_quant_rows_e4m3", "mrag_gemm_fp8", "mrag_fp8_launch_counts", "mrag_conv_fp8", "mrag_conv_fp8_launch_counts",
 ]
 
 
@@ -158,6 +158,14 @@ class ConvArgs(Structure):
         ("N", c_int32), ("H", c_int32), ("Wd", c_int32), ("Cin", c_int32), ("Cout", c_int32),
         ("stride", c_int32), ("upsample", c_int32), ("mode", c_int32), ("epilogue", c_int32), ("asym_pad", c_int32),
         ("t_taps", c_int32), ("t_frames", c_int32), ("acc_scale", c_float),
+    ]
+
+
+class ConvFp8Args(Structure):
+    _fields_ = [
+        ("x8", c_void_p), ("W8", c_void_p), ("x_exp", c_void_p), ("w_exp", c_void_p), ("bias", c_void_p), ("y", c_void_p), ("resid", c_void_p),
+        ("N", c_int32), ("H", c_int32), ("Wd", c_int32), ("Cin", c_int32), ("Cout", c_int32),
+        ("stride", c_int32), ("upsample", c_int32), ("asym_pad", c_int32), ("t_taps", c_int32), ("epilogue", c_int32),
     ]
 
 
@@ -313,6 +321,8 @@ def lib() -> ctypes.CDLL:
     L.mrag_add_rows_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64]
     L.mrag_add_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]
     L.mrag_conv_bf16.argtypes = [c_void_p, POINTER(ConvArgs)]
+    L.mrag_conv_fp8.argtypes = [c_void_p, POINTER(ConvFp8Args)]
+    L.mrag_conv_fp8_launch_counts.argtypes = [c_void_p, c_int32]
     L.mrag_ip_attn_folded_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64,
                                            c_int64, c_float, c_float, c_int32]
     L.mrag_add_bcast_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64]

@@ -72,6 +72,25 @@ def host_scalar(fn, p: torch.Tensor) -> float:
     return CACHE.get(("scalar", fn, id(p)), p, lambda: float(fn(p.detach().float()).item()))
 
 
+CONV_PRECISION_ATTR = "_mrag_conv_precision"
+# a marked convolution takes the fp8 kernel from this many 256x256 output tiles on (the `t256 >= 192` of gemm_conv.hip: below it the bf16 path runs
+# 128x128 tiles that fill the device, the fp8 kernel's one tile shape does not); tests of reduced models set it to 0
+CONV_FP8_MIN_TILES = 192
+
+
+def set_conv_precision(module: nn.Module, precision: str = "bf16") -> nn.Module:
+    """precision of the 3x3 convolutions under `module` that run through `conv3x3` (the UNets' ResBlocks, the VAE decoders' ResnetBlocks):
+    "bf16" (default, the reference precision) or "fp8" -- the e4m3 implicit GEMM (mrag_conv_fp8: per-pixel activation exponents, per-output-channel
+    weight exponents, fp32 accumulation) wherever `ops.conv_fp8_supported` admits the call and it makes at least CONV_FP8_MIN_TILES
+    output tiles of 256x256; stride-2, upsampling and temporal convolutions and those from or to 3, 4 or 8 channels stay bf16 through that gate.  Marks every nn.Conv2d with a 3x3 kernel; returns the module."""
+    if precision not in ("bf16", "fp8"):
+        raise ValueError(f"conv precision must be 'bf16' or 'fp8', got {precision!r}")
+    for m in module.modules():
+        if isinstance(m, nn.Conv2d) and tuple(m.kernel_size) == (3, 3):
+            setattr(m, CONV_PRECISION_ATTR, precision)
+    return module
+
+
 def conv3x3(x: torch.Tensor, conv: nn.Conv2d, *, stride: int = 1, upsample: bool = False, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [N, H, W, Cin] -> [N, Ho, Wo, Cout]: implicit GEMM over gathered rows; `resid` (same shape as the output) fused in the epilogue."""
     N, H, W, C = x.shape
@@ -85,6 +104,11 @@ def conv3x3(x: torch.Tensor, conv: nn.Conv2d, *, stride: int = 1, upsample: bool
         return w.contiguous()
 
     wk = CACHE.get(("c3", id(conv)), conv.weight, build)
+    if (getattr(conv, CONV_PRECISION_ATTR, "bf16") == "fp8" and ops.conv_fp8_supported(N, H, W, C, cout, stride, upsample)
+            and ((N * H * W + 255) // 256) * ((cout + 255) // 256) >= CONV_FP8_MIN_TILES):
+        # opt-in e4m3 path (set_conv_precision): the weight quantised once per output channel, the activation per pixel in front of the launch
+        w8, w_exp = CACHE.get(("c3f8", id(conv)), conv.weight, lambda: ops.quant_rows_e4m3(bf16(wk)))
+        return ops.conv_implicit_fp8(x.contiguous(), w8, w_exp, conv.bias, resid=resid.contiguous() if resid is not None else None)
     if C % 64 == 0:                                                                 # implicit GEMM: the GEMM's DMA gathers the taps itself
         return ops.conv_implicit(x.contiguous(), wk, conv.bias, ops.CONV_3X3, stride=stride, upsample=upsample,
                                  resid=resid.contiguous() if resid is not None else None)

@@ -922,6 +922,66 @@ def conv_implicit(x: torch.Tensor, wk: torch.Tensor, bias: Optional[torch.Tensor
     return out
 
 
+def conv_fp8_launch_counts() -> dict:
+    """launches of the fp8 convolution so far (host-side counter, mrag_conv_fp8_launch_counts): {"conv": n}"""
+    buf = (ctypes.c_uint64 * 1)()
+    _lib.lib().mrag_conv_fp8_launch_counts(buf, 1)
+    return {"conv": int(buf[0])}
+
+
+def conv_fp8_supported(N: int, H: int, W: int, Cin: int, Cout: int, stride: int = 1, upsample: bool = False) -> bool:
+    """the shapes mrag_conv_fp8 takes (include/mrag_hip.h): the plain 3x3, stride 1, padding 1 convolution at Cin % 64 == 0, Cout % 4 == 0 and Cout > 8, inside the
+    kernel's 32-bit source offsets.  Everything else stays on the bf16 implicit GEMM."""
+    if min(N, H, W, Cin, Cout) < 1 or stride != 1 or upsample:
+        return False
+    if Cin % 64 != 0 or Cout % 4 != 0 or Cout <= 8:                     # (to 4 or 8 channels: the convolutions that write a model's output stay bf16)
+        return False
+    HW = H * W
+    if H > 32767 or W > 32767 or N * HW > 2 ** 31 - 1:
+        return False
+    return (255 // HW + 2) * HW * Cin < 2 ** 31 and Cout * 9 * Cin < 2 ** 32
+
+
+def conv_implicit_fp8(x: torch.Tensor, w8: torch.Tensor, w_exp: torch.Tensor, bias: Optional[torch.Tensor], resid: Optional[torch.Tensor] = None, *,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nn.Conv2d(Cin, Cout, 3, stride 1, padding 1) on the e4m3 MFMA path: x [N, H, W, Cin] bf16 is quantised per pixel (`quant_rows_e4m3`) into a
+    grow-only workspace of the (device, stream); (w8, w_exp) = quant_rows_e4m3 of the [Cout, 9 Cin] tap-major weight, once per output channel.
+    `resid` (the output's shape) rides in the epilogue; `out` may be `resid`.  Two launches, nothing read back: capturable into a HIP graph.  Raises on shapes the kernel does
+    not take (`conv_fp8_supported`)."""
+    from ._lib import ConvFp8Args
+    _dev(x, name="x"); _dev(w8, torch.uint8, "w8"); _dev(w_exp, torch.int32, "w_exp")
+    if bias is not None:
+        _dev(bias, name="bias")
+    if x.dim() != 4 or not x.is_contiguous() or not w8.is_contiguous() or not w_exp.is_contiguous():
+        raise ValueError("conv_implicit_fp8: contiguous x [N, H, W, Cin], w8 and w_exp required")
+    N, H, W, C = x.shape
+    cout = w8.shape[0]
+    if tuple(w8.shape) != (cout, 9 * C) or tuple(w_exp.shape) != (cout,):
+        raise ValueError(f"conv_implicit_fp8: w8 {tuple(w8.shape)} / w_exp {tuple(w_exp.shape)} do not match 9 taps x {C} channels")
+    if not conv_fp8_supported(N, H, W, C, cout):
+        raise ValueError(f"conv_implicit_fp8: {tuple(x.shape)} -> {cout} channels is outside the fp8 convolution's shapes")
+    M = N * H * W
+    exp_bytes = (M * 4 + 255) // 256 * 256
+    ws = _attn_workspace(x.device, exp_bytes + M * C, "fp8conv")
+    x_exp, x8 = ws[:M * 4].view(torch.int32), ws[exp_bytes:exp_bytes + M * C].view(M, C)
+    quant_rows_e4m3(x.view(M, C), out=(x8, x_exp))
+    if out is None:
+        out = torch.empty(N, H, W, cout, dtype=torch.bfloat16, device=x.device)
+    elif _dev(out, name="out").numel() != M * cout or not out.is_contiguous():
+        raise ValueError("conv_implicit_fp8: out must be contiguous [N, H, W, Cout]")
+    a = ConvFp8Args()
+    a.x8, a.W8, a.x_exp, a.w_exp, a.bias, a.y = _p(x8), _p(w8), _p(x_exp), _p(w_exp), _p(bias), _p(out)
+    a.N, a.H, a.Wd, a.Cin, a.Cout = N, H, W, C, cout
+    a.stride, a.epilogue = 1, EPI_NONE
+    if resid is not None:
+        _dev(resid, name="resid")
+        if resid.numel() != out.numel() or not resid.is_contiguous():
+            raise ValueError("conv_implicit_fp8: resid must be contiguous with the output's shape")
+        a.resid, a.epilogue = _p(resid), EPI_RESID
+    check(_lib.lib().mrag_conv_fp8(_stream(), ctypes.byref(a)), "mrag_conv_fp8")
+    return out
+
+
 def _kpad(k: int) -> int:
     return (k + 63) // 64 * 64
 
