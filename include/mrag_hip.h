@@ -245,6 +245,31 @@ int mrag_gemm_fp8(void* stream, const mrag_gemm_fp8_args* args);
  * whose enumerators are pinned: copies min(n, 2) of them into out_host (HOST memory) and returns 2.  Tests prove with them that the fp8 kernel ran. */
 int mrag_fp8_launch_counts(uint64_t* out_host, int32_t n);
 
+/* The UNets' feed-forward linears on the same path -- OPT-IN (layers.set_ff_precision): the GEGLU projection and the output projection of the
+ * DynamiCrafter / SVD transformer blocks' FeedForward (lvdm attention.py:448-475, diffusers FeedForward), whose level-0 width K = 320 is 2.5 K-tiles.
+ *
+ * mrag_layernorm_e4m3: y = LayerNorm(x) * gamma + beta over the last dim of x [M, K] bf16 (row stride ldx; gamma / beta [K] bf16 or NULL), written as
+ * x8 [M, K] e4m3fn bytes (row stride ld8, bytes) and exp [M] -- bit for bit what mrag_quant_rows_e4m3 makes of mrag_layernorm_bf16's output on the same
+ * arguments: the normalised value is rounded to bf16 first, then exp[m] and the round-to-nearest-even of the exact product as above (0 for an all-zero
+ * row, clamped to +-60).  The rounding to bf16 in the middle is part of the contract: the fp8 path's numbers do not depend on whether this fusion ran.
+ * One pass over x, no workspace, nothing read back; the bf16 row is never written.  MRAG_ENOTSUP (run the two launches instead) unless K % 16 == 0,
+ * K <= 2048 (the row stays in registers) and the rows of x and x8 and gamma / beta are 16-byte aligned (ldx % 8 == 0, ld8 % 16 == 0);
+ * MRAG_EINVAL for null x / x8 / exp or M, K < 1.                                                                                                */
+int mrag_layernorm_e4m3(void* stream, const void* x, const void* gamma, const void* beta, float eps, void* x8, int32_t* exp, int64_t M, int64_t K,
+                        int64_t ldx, int64_t ld8);
+/* mrag_gemm_fp8 for K % 64 == 0 and with the GEGLU epilogue, on the same argument block (gate0 / gate1 and the row-range fields are not read).
+ * K % 128 == 64: the last K-tile is one 64-deep MFMA step; no byte behind a row's K bytes is read, of A8's and W8's last rows either.  Accumulation
+ * stays in ascending 64-deep steps: with MRAG_EPI_NONE / MRAG_EPI_RESID the result is bit-identical to mrag_gemm_fp8 at K % 128 == 0, and otherwise to
+ * mrag_gemm_fp8 on the operands zero-padded to the next multiple of 128.
+ * MRAG_EPI_GEGLU (exact erf): C [M, N / 2], ldc >= N / 2; W8 / w_exp / bias rows in the 32-row groups of 16 value then 16 gate rows that the bf16
+ * GEMM's MRAG_EPI_GEGLU reads (ops.geglu_interleave); C[m, j] = bf16( bf16(value_j) * gelu(bf16(gate_j)) ), the rounding points of the bf16 epilogue.
+ * MRAG_ENOTSUP unless K % 64 == 0 and N % 16 == 0 (MRAG_EPI_GEGLU: N % 32 == 0), and for every epilogue but MRAG_EPI_NONE, MRAG_EPI_RESID and
+ * MRAG_EPI_GEGLU; MRAG_EINVAL for null or misaligned pointers, as mrag_gemm_fp8.  C may alias resid.                                          */
+int mrag_gemm_fp8_k64(void* stream, const mrag_gemm_fp8_args* args);
+/* host-side relaxed launch counters in the form of mrag_fp8_launch_counts (whose two slots keep their meaning): slot 0 counts mrag_gemm_fp8_k64
+ * launches, slot 1 mrag_layernorm_e4m3 launches (not its MRAG_ENOTSUP returns).  Copies min(n, 2) slots into out_host (HOST memory), returns 2. */
+int mrag_gemm_fp8_k64_launch_counts(uint64_t* out_host, int32_t n);
+
 /* ------------------------------------------------------------------------ */
 /* Attention, head_dim 64, bf16, flash-style (no S x S matrix in HBM).       */
 /*   O[b, sq, h*64+d] = resid + out_scale * softmax(Q K^T * scale [+mask]) V */

@@ -37,6 +37,7 @@ SYMBOLS = [
     "mrag_resize_patchify_bf16", "mrag_assemble_tokens_bf16", "mrag_softmax_rows_bf16", "mrag_denormalize_u8", "mrag_attn_small_bf16", "mrag_blend_tile_bf16", "mrag_cfg_dpm_step_bf16",
     "mrag_resampler_workspace_bytes", "mrag_resampler_fwd", "mrag_cama_encoder_workspace_bytes", "mrag_cama_encoder_fwd",
     "mrag_quant_rows_e4m3", "mrag_gemm_fp8", "mrag_fp8_launch_counts", "mrag_conv_fp8", "mrag_conv_fp8_launch_counts",
+    "mrag_layernorm_e4m3", "mrag_gemm_fp8_k64", "mrag_gemm_fp8_k64_launch_counts",
 ]
 
 
@@ -299,6 +300,9 @@ def lib() -> ctypes.CDLL:
     L.mrag_quant_rows_e4m3.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64]
     L.mrag_gemm_fp8.argtypes = [c_void_p, POINTER(GemmFp8Args)]
     L.mrag_fp8_launch_counts.argtypes = [c_void_p, c_int32]
+    L.mrag_layernorm_e4m3.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64]
+    L.mrag_gemm_fp8_k64.argtypes = [c_void_p, POINTER(GemmFp8Args)]
+    L.mrag_gemm_fp8_k64_launch_counts.argtypes = [c_void_p, c_int32]
     L.mrag_gemm_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
     L.mrag_gemm_workspace_bytes.restype = c_int64
     L.mrag_attn_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]

@@ -93,6 +93,26 @@ __device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d
   unsigned r = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0u, false);
   return __builtin_amdgcn_cvt_pk_fp8_f32(c, d, r, true);
 }
+// running maximum of |x| over 8 packed bf16, as fp32 bits (integer order == float order for non-negative floats)
+__device__ __forceinline__ unsigned absmax8(unsigned m, const u32x4 v) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned lo = (v[i] << 16) & 0x7fff0000u, hi = v[i] & 0x7fff0000u;   // |x| as fp32 bits: integer order == float order
+    m = lo > m ? lo : m;
+    m = hi > m ? hi : m;
+  }
+  return m;
+}
+// 8 packed bf16 * mul -> 8 e4m3 bytes (the arithmetic of gemm_fp8.hip's quant16: the exact product, rounded to nearest even)
+__device__ __forceinline__ u32x2 quant8_fp8(const u32x4 a, const float mul) {
+  float f[8];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    f[2 * j] = __uint_as_float(a[j] << 16) * mul;
+    f[2 * j + 1] = __uint_as_float(a[j] & 0xffff0000u) * mul;
+  }
+  return u32x2{pack4_fp8(f[0], f[1], f[2], f[3]), pack4_fp8(f[4], f[5], f[6], f[7])};
+}
 
 // async global -> LDS copy of 16 bytes per lane; LDS destination is
 // wave-uniform base + lane*16 (cdna_hip_programming.md section 5 caveat).

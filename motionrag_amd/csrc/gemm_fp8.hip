@@ -7,6 +7,11 @@
 //                          MFMA rate, half the LDS / DMA bytes).  The row exponents ride the instruction's E8M0 scale operands (127 - e per lane: a lane's
 //                          scale byte applies to its own row's 32 k's), which undoes both power-of-two scales for free, as attn8_kernel does with scale_q.
 //
+//   mrag_gemm_fp8_k64      the same kernel for the UNets' feed-forward linears (layers.set_ff_precision): K % 64 == 0 -- at K % 128 == 64 the last
+//                          K-tile is ONE 64-deep MFMA step, its DMA lanes of the absent half re-read the present half (inside the row: nothing behind
+//                          the last row of A8 or W8 is touched) into LDS bytes no fragment read visits -- and MRAG_EPI_GEGLU: W rows in ops.geglu_interleave's
+//                          32-row groups (16 value | 16 gate) put a lane's values in register quads 0, 1 and their gates in quads 2, 3 of one accumulator.
+//
 // Kernel shape: a 256x256 tile on 8 waves (2 x 4, 128 rows x 64 columns each: 4 x 2 accumulators of 32x32), K-tiles of 128 bytes, two LDS stages of
 // 64 KiB filled by 16-byte global_load_lds in 1-KiB pieces (8 rows x 128 B) with the XOR swizzle on the SOURCE address (chunk ^= row & 7) and on the
 // ds_read_b128 -- the LDS image and idiom of gemm_tile.h with bytes for bf16 pairs.  The DMA of K-tile t + 1 is issued behind the barrier that opens
@@ -20,20 +25,12 @@
 
 // host-side relaxed launch counters (mrag_fp8_launch_counts): slot 0 the GEMM, slot 1 the row quantiser
 static unsigned long long g_fp8_launches[2];
+// mrag_gemm_fp8_k64_launch_counts: slot 0 mrag_gemm_fp8_k64, slot 1 mrag_layernorm_e4m3 (norm.hip counts into it)
+unsigned long long g_fp8_k64_launches[2];
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ row quantiser
-__device__ __forceinline__ unsigned absmax8(unsigned m, const u32x4 v) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const unsigned lo = (v[i] << 16) & 0x7fff0000u, hi = v[i] & 0x7fff0000u;   // |x| as fp32 bits: integer order == float order
-    m = lo > m ? lo : m;
-    m = hi > m ? hi : m;
-  }
-  return m;
-}
-
 __device__ __forceinline__ u32x4 quant16(const u32x4 a, const u32x4 b, const float mul) {
   float f[16];
 #pragma unroll
@@ -105,7 +102,8 @@ constexpr int G8_ROWB = 144;                               // staged epilogue: r
 constexpr int G8_LDS = 8 * 128 * G8_ROWB;                  // 144 KiB: the epilogue's per-wave regions overlay the two operand stages (128 KiB)
 static_assert(G8_LDS >= 2 * G8_STAGE, "the operand stages fit the allocation");
 
-template <int EPI>
+// K64 (mrag_gemm_fp8_k64): p.K % 64 == 0, a last half K-tile is one MFMA step; EPI may be MRAG_EPI_GEGLU (C [M, N / 2])
+template <int EPI, bool K64 = false>
 __global__ __launch_bounds__(512) void gemm_fp8_kernel(const Gemm8P p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NW = 8, PPW = (G8_BM + G8_BN) / 8 / NW;     // 64 pieces of 1 KiB per stage, 8 per wave: the first 4 are A rows, the others W rows
@@ -137,10 +135,14 @@ __global__ __launch_bounds__(512) void gemm_fp8_kernel(const Gemm8P p) {
       gsrc[i] = p.W + row * p.ldw + chunk * 16;
     }
   }
-  auto issue = [&](int stage, int kt) {
+  // K64, last half K-tile: the row has 64 bytes left, so the lanes of chunks 4 .. 7 fetch chunks 0 .. 3 again (a lane's chunk is the same in all its pieces)
+  const bool half = K64 && (p.K % G8_BK) != 0;
+  const int half_back = (((lane & 7) ^ (lane >> 3)) >= 4) ? -64 : 0;
+  auto issue = [&](int stage, int kt, bool clamp = false) {
     char* base = smem + stage * G8_STAGE;
+    const long long off = (long long)kt * G8_BK + (clamp ? half_back : 0);
 #pragma unroll
-    for (int i = 0; i < PPW; ++i) glds16(gsrc[i] + (long long)kt * G8_BK, base + (wave + i * NW) * 1024);
+    for (int i = 0; i < PPW; ++i) glds16(gsrc[i] + off, base + (wave + i * NW) * 1024);
   };
 
   // E8M0 scale operands: the lane's W row (A operand) and activation row (B operand) of every 32-row block
@@ -198,16 +200,17 @@ __global__ __launch_bounds__(512) void gemm_fp8_kernel(const Gemm8P p) {
     acc[I][1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(MRAG8_FRAG(W[2], W[3]), af, acc[I][1], 0, 0, 0, sw[1], 0, sa[I]); \
   } while (0)
 
-  const int nk = (int)(p.K / G8_BK);
-  issue(0, 0);
+  const int nk = (int)((p.K + (K64 ? G8_BK - 1 : 0)) / G8_BK);
+  issue(0, 0, half && nk == 1);
   for (int kt = 0; kt < nk; ++kt) {
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");   // tile kt landed for every wave; every wave finished reading the other stage
     const unsigned so = (unsigned)((kt & 1) * G8_STAGE);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
+      if (K64 && ks == 1 && half && kt == nk - 1) break;             // (workgroup-uniform) the half tile has no second step
       u32x4 w[4], a[8];
       MRAG8_READ12(w, a, rowW + so + ca[ks][0], rowW + so + ca[ks][1], rowA + so + ca[ks][0], rowA + so + ca[ks][1]);
-      if (ks == 0 && kt + 1 < nk) issue((kt + 1) & 1, kt + 1);      // the next tile's eight DMA requests go out under the first fragments' LDS latency
+      if (ks == 0 && kt + 1 < nk) issue((kt + 1) & 1, kt + 1, half && kt + 2 == nk);    // the next tile's eight DMA requests go out under the first fragments' LDS latency
       // the order below is the schedule (hipcc would gather the four waits in front of the first MFMA): each pair of MFMAs starts when ITS rows are here
       __builtin_amdgcn_sched_barrier(0);
       MRAG8_WAIT_WA(6, w, a[0], a[1]);
@@ -253,6 +256,32 @@ __global__ __launch_bounds__(512) void gemm_fp8_kernel(const Gemm8P p) {
       row_bp(m < p.M ? m : p.M - 1, b, pos);
       gate = (pos < p.split ? p.gate0 : p.gate1) + b * p.gate_stride;
     }
+    if constexpr (EPI == MRAG_EPI_GEGLU) {
+      // accumulator j is one 32-row group of W: quads 0, 1 hold the values of output columns 8 g + 4 hh .. + 3 of the group's 16, quads 2, 3 their gates
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          long long n = bn0 + wn * 64 + j * 32 + 8 * g + 4 * hh;
+          n = n < p.N ? n : p.N - 32 + 8 * g + 4 * hh;   // (N % 32 == 0: the gate column n + 16 exists with the value column) clamped columns are never stored
+          float v[4] = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+          float gt[4] = {acc[i][j][4 * g + 8], acc[i][j][4 * g + 9], acc[i][j][4 * g + 10], acc[i][j][4 * g + 11]};
+          if (p.bias) {
+            const u32x2 bv = *(const u32x2*)(p.bias + n), bg = *(const u32x2*)(p.bias + n + 16);
+            v[0] += __uint_as_float(bv[0] << 16); v[1] += __uint_as_float(bv[0] & 0xffff0000u);
+            v[2] += __uint_as_float(bv[1] << 16); v[3] += __uint_as_float(bv[1] & 0xffff0000u);
+            gt[0] += __uint_as_float(bg[0] << 16); gt[1] += __uint_as_float(bg[0] & 0xffff0000u);
+            gt[2] += __uint_as_float(bg[1] << 16); gt[3] += __uint_as_float(bg[1] & 0xffff0000u);
+          }
+          geglu4<false>(v, gt);
+          u32x2 out;
+          out[0] = pack_bf2(v[0], v[1]);
+          out[1] = pack_bf2(v[2], v[3]);
+          *(u32x2*)(wbase + lrow * G8_ROWB + (j * 16 + 8 * g + 4 * hh) * 2) = out;
+        }
+      }
+      continue;
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
 #pragma unroll
@@ -279,6 +308,20 @@ __global__ __launch_bounds__(512) void gemm_fp8_kernel(const Gemm8P p) {
         *(u32x2*)(wbase + lrow * G8_ROWB + lcol * 2) = out;
       }
     }
+  }
+  if constexpr (EPI == MRAG_EPI_GEGLU) {
+    // the wave's 128 x 32 outputs: lane -> row (lane >> 2) of a 16-row group, 16-byte chunk (lane & 3); one instruction = 16 x 64 contiguous bytes
+    const int rsub = lane >> 2, chunk = lane & 3;
+    const long long n = (bn0 + wn * 64) / 2 + chunk * 8;
+    const bool n_ok = n + 8 <= p.N / 2;
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      const int row = g * 16 + rsub;
+      const long long m = bm0 + wm * 128 + row;
+      const u32x4 val = *(const u32x4*)(wbase + row * G8_ROWB + chunk * 16);
+      if (m < p.M && n_ok) *(u32x4*)(p.C + m * p.ldc + n) = val;
+    }
+    return;
   }
   // row layout: lane -> row (lane >> 3) of an 8-row group, 16-byte chunk (lane & 7); one instruction = 8 x 128 contiguous bytes
   const int rsub = lane >> 3, chunk = lane & 7;
@@ -332,6 +375,45 @@ extern "C" int mrag_quant_rows_e4m3(void* stream, const void* x, void* x8, int32
   }
   MRAG_LAUNCH_CHECK();
   (void)__atomic_fetch_add(&g_fp8_launches[1], 1ull, __ATOMIC_RELAXED);
+  return MRAG_OK;
+}
+
+extern "C" int mrag_gemm_fp8_k64_launch_counts(uint64_t* out_host, int32_t n) {
+  for (int i = 0; out_host && i < n && i < 2; ++i) out_host[i] = __atomic_load_n(&g_fp8_k64_launches[i], __ATOMIC_RELAXED);
+  return 2;
+}
+
+extern "C" int mrag_gemm_fp8_k64(void* stream, const mrag_gemm_fp8_args* a) {
+  if (!a || !a->A8 || !a->W8 || !a->a_exp || !a->w_exp || !a->C) return MRAG_EINVAL;
+  if (a->M < 1 || a->N < 1 || a->K < 1) return MRAG_EINVAL;
+  const int epi = a->epilogue;
+  if (epi != MRAG_EPI_NONE && epi != MRAG_EPI_RESID && epi != MRAG_EPI_GEGLU) return MRAG_ENOTSUP;
+  const bool glu = epi == MRAG_EPI_GEGLU, res = epi == MRAG_EPI_RESID;
+  if (a->K % 64 != 0 || a->N % (glu ? 32 : 16) != 0) return MRAG_ENOTSUP;
+  const long long ncols = glu ? a->N / 2 : a->N;             // columns of C
+  if (a->lda < a->K || a->ldw < a->K || a->ldc < ncols) return MRAG_EINVAL;
+  // the pointer and alignment checks of mrag_gemm_fp8
+  if ((((uintptr_t)a->A8 | (uintptr_t)a->W8) & 15) || a->lda % 16 != 0 || a->ldw % 16 != 0) return MRAG_EINVAL;
+  if ((((uintptr_t)a->a_exp | (uintptr_t)a->w_exp) & 3) || (a->bias && ((uintptr_t)a->bias & 7))) return MRAG_EINVAL;
+  if (res && (!a->resid || a->ldr < a->N)) return MRAG_EINVAL;
+  if (!rows_16B_aligned(a->C, a->ldc, res ? a->resid : nullptr, a->ldr)) return MRAG_EINVAL;
+  const long long tiles_m = (a->M + G8_BM - 1) / G8_BM, tiles_n = (a->N + G8_BN - 1) / G8_BN;
+  if (tiles_m * tiles_n > 0x7fffffffll) return MRAG_ENOTSUP;
+  Gemm8P p{};
+  p.A = (const uint8_t*)a->A8; p.W = (const uint8_t*)a->W8; p.ea = a->a_exp; p.ew = a->w_exp;
+  p.bias = (const bf16_t*)a->bias; p.C = (bf16_t*)a->C; p.resid = res ? (const bf16_t*)a->resid : nullptr;
+  p.M = a->M; p.N = a->N; p.K = a->K; p.lda = a->lda; p.ldw = a->ldw; p.ldc = a->ldc; p.ldr = a->ldr;
+  p.tiles_m = (int)tiles_m; p.tiles_n = (int)tiles_n; p.group_m = 4;
+  const dim3 grid((unsigned)(tiles_m * tiles_n)), block(512);
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  switch (epi) {
+    case MRAG_EPI_NONE: rc = launch_dyn_lds(gemm_fp8_kernel<MRAG_EPI_NONE, true>, grid, block, G8_LDS, s, p); break;
+    case MRAG_EPI_RESID: rc = launch_dyn_lds(gemm_fp8_kernel<MRAG_EPI_RESID, true>, grid, block, G8_LDS, s, p); break;
+    default: rc = launch_dyn_lds(gemm_fp8_kernel<MRAG_EPI_GEGLU, true>, grid, block, G8_LDS, s, p); break;
+  }
+  if (rc != MRAG_OK) return rc;
+  (void)__atomic_fetch_add(&g_fp8_k64_launches[0], 1ull, __ATOMIC_RELAXED);
   return MRAG_OK;
 }
 

@@ -7,6 +7,9 @@
 // persistent workgroups per CU of layernorm_stream_kernel: with the next row prefetched the kernel holds 144 registers of row + per-column vectors
 constexpr int LN_STREAM_WGS = 2;
 
+// mrag_gemm_fp8_k64_launch_counts (gemm_fp8.hip): slot 1 counts mrag_layernorm_e4m3
+extern unsigned long long g_fp8_k64_launches[2];
+
 namespace {
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -35,10 +38,13 @@ struct LnP {
   long long rows, D, ldx, ldy, rows_per_batch, split, mod_stride, y_rpb, y_bstride;
   float eps;
   int rms;   // RMSNorm (T5LayerNorm): no mean subtraction, variance = mean(x^2)
+  uint8_t* x8; int* exps; long long ld8;   // the Q8 kernels (mrag_layernorm_e4m3): e4m3 rows and their exponents in place of y
 };
 
 // y = LN(x) * gamma + beta ; y = y * (1 + scale[b]) + shift[b]
-template <int MAXC>
+// Q8 (mrag_layernorm_e4m3): the row rounded to bf16 stays in registers, its amax is reduced in the wave and the row leaves as e4m3 * 2^exp --
+// the bits mrag_quant_rows_e4m3 makes of this kernel's y, which is never written
+template <int MAXC, bool Q8 = false>
 __global__ __launch_bounds__(256) void layernorm_kernel(const LnP p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long row = (long long)blockIdx.x * 4 + wave;
@@ -78,6 +84,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const LnP p) {
     scale = ((long long)pos < p.split ? p.scale0 : p.scale1) + (long long)b * p.mod_stride;
   }
   bf16_t* y = p.y_rpb > 0 ? p.y + (long long)((unsigned)row / (unsigned)p.y_rpb) * p.y_bstride + (long long)((unsigned)row % (unsigned)p.y_rpb) * p.ldy : p.y + row * p.ldy;
+  u32x4 q[Q8 ? MAXC : 1];
+  unsigned amax = 0;
 #pragma unroll
   for (int c = 0; c < MAXC; ++c) {
     const long long idx = ((long long)c * 64 + lane) * 8;
@@ -102,7 +110,21 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const LnP p) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = __builtin_fmaf(o[e], __fadd_rn(1.0f, sc[e]), sh[e]);   // (explicit: layernorm_stream_kernel repeats this arithmetic bit for bit)
     }
-    __builtin_nontemporal_store(pack8(o), (u32x4*)(y + idx));
+    if constexpr (Q8) { q[c] = pack8(o); amax = absmax8(amax, q[c]); }
+    else __builtin_nontemporal_store(pack8(o), (u32x4*)(y + idx));
+  }
+  if constexpr (Q8) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { const unsigned s = __shfl_xor(amax, o); amax = s > amax ? s : amax; }
+    const int e = pow2_fit(__uint_as_float(amax));
+    const float mul = ldexpf(1.0f, e);
+    if (lane == 0) p.exps[row] = e;
+    uint8_t* dst = p.x8 + row * p.ld8;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+      const long long idx = ((long long)c * 64 + lane) * 8;
+      if (idx < p.D) *(u32x2*)(dst + idx) = quant8_fp8(q[c], mul);
+    }
   }
 }
 
@@ -203,7 +225,8 @@ __global__ __launch_bounds__(256, LN_STREAM_WGS) void layernorm_stream_kernel(co
 // chunks each, chunk index = sub-lane + LPR c: the LPR lanes of a row read 16 LPR contiguous bytes per instruction), so a wave normalises 8 / 4 / 2 rows with every
 // lane busy.  Plain LayerNorm only (gamma / beta, output row remap; no AdaLN modulation, no RMS form: those stay on layernorm_kernel); the same two-pass
 // statistics in registers, summed over another lane partition -- results agree with layernorm_kernel to fp32 rounding of the statistics.
-template <int LPR, int CH>
+// Q8: as layernorm_kernel's, the amax over the row's LPR lanes.
+template <int LPR, int CH, bool Q8 = false>
 __global__ __launch_bounds__(256) void layernorm_rows_kernel(const LnP p) {
   constexpr int RPW = 64 / LPR;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane % LPR, rs = lane / LPR;
@@ -230,6 +253,8 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const LnP p) {
   for (int o = LPR / 2; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
   const float rstd = rsqrtf(sq / (float)p.D + p.eps);
   bf16_t* y = p.y_rpb > 0 ? p.y + (long long)((unsigned)row / (unsigned)p.y_rpb) * p.y_bstride + (long long)((unsigned)row % (unsigned)p.y_rpb) * p.ldy : p.y + row * p.ldy;
+  u32x4 q[Q8 ? CH : 1];
+  unsigned amax = 0;
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
     const int idx = (sub + LPR * c) * 8;
@@ -246,7 +271,19 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const LnP p) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] += bb[e];
     }
-    if (row0 < p.rows) __builtin_nontemporal_store(pack8(o), (u32x4*)(y + idx));
+    if constexpr (Q8) { q[c] = pack8(o); amax = absmax8(amax, q[c]); }
+    else if (row0 < p.rows) __builtin_nontemporal_store(pack8(o), (u32x4*)(y + idx));
+  }
+  if constexpr (Q8) {
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) { const unsigned s = __shfl_xor(amax, o); amax = s > amax ? s : amax; }
+    const int e = pow2_fit(__uint_as_float(amax));
+    const float mul = ldexpf(1.0f, e);
+    if (row0 >= p.rows) return;
+    if (sub == 0) p.exps[row] = e;
+    uint8_t* dst = p.x8 + row * p.ld8;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) *(u32x2*)(dst + (sub + LPR * c) * 8) = quant8_fp8(q[c], mul);
   }
 }
 
@@ -321,6 +358,9 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(const QkP p) {
 
 }  // namespace
 
+// plain LayerNorms that run layernorm_rows_kernel (mrag_layernorm_e4m3 follows mrag_layernorm_bf16 kernel for kernel: their statistics differ in fp32 rounding)
+static bool ln_narrow_rows(long long D, long long rows) { return (D == 320 || D == 640 || D == 1280 || D == 1024) && rows >= 1024; }
+
 extern "C" int mrag_layernorm_bf16(void* stream, const mrag_ln_args* a) {
   if (!a || !a->x || !a->y || a->rows <= 0 || a->D <= 0) return MRAG_EINVAL;
   if (a->D % 8 != 0 || a->ldx % 8 != 0 || a->ldy % 8 != 0) return MRAG_EINVAL;
@@ -338,7 +378,7 @@ extern "C" int mrag_layernorm_bf16(void* stream, const mrag_ln_args* a) {
   if (p.y_rpb < 0 || (p.y_rpb > 0 && p.y_bstride % 8 != 0)) return MRAG_EINVAL;
   const dim3 grid((unsigned)((a->rows + 3) / 4)), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (!a->shift0 && !a->rms && (a->D == 320 || a->D == 640 || a->D == 1280 || a->D == 1024) && a->rows >= 1024) {   // narrow rows: several rows per wave
+  if (!a->shift0 && !a->rms && ln_narrow_rows(a->D, a->rows)) {   // narrow rows: several rows per wave
     if (a->D == 320) MRAG_LAUNCH((layernorm_rows_kernel<8, 5>), dim3((unsigned)((a->rows + 31) / 32)), block, 0, s, p);
     else if (a->D == 640) MRAG_LAUNCH((layernorm_rows_kernel<16, 5>), dim3((unsigned)((a->rows + 15) / 16)), block, 0, s, p);
     else if (a->D == 1024) MRAG_LAUNCH((layernorm_rows_kernel<16, 8>), dim3((unsigned)((a->rows + 15) / 16)), block, 0, s, p);   // CAMA's media rows (15 680 x 1 024, into the K/V concat buffer): 36 -> ? us
@@ -362,6 +402,33 @@ extern "C" int mrag_layernorm_bf16(void* stream, const mrag_ln_args* a) {
   else MRAG_LAUNCH(layernorm_kernel<16>, grid, block, 0, s, p);
   MRAG_LAUNCH_CHECK();
   MRAG_COUNT(MRAG_K_LAYERNORM);
+  return MRAG_OK;
+}
+
+extern "C" int mrag_layernorm_e4m3(void* stream, const void* x, const void* gamma, const void* beta, float eps, void* x8, int32_t* exp, int64_t M,
+                                   int64_t K, int64_t ldx, int64_t ld8) {
+  if (!x || !x8 || !exp || M < 1 || K < 1 || M >= (1LL << 31)) return MRAG_EINVAL;
+  // K <= 2048: the row and its bf16 copy stay in registers (layernorm_kernel<4>); aligned as mrag_layernorm_bf16 and mrag_quant_rows_e4m3 ask
+  if (K % 16 != 0 || K > 2048 || ldx % 8 != 0 || ld8 % 16 != 0 || ldx < K || ld8 < K) return MRAG_ENOTSUP;
+  if ((((uintptr_t)x | (uintptr_t)x8 | (uintptr_t)gamma | (uintptr_t)beta) & 15) || ((uintptr_t)exp & 3)) return MRAG_ENOTSUP;
+  LnP p{};
+  p.x = (const bf16_t*)x; p.gamma = (const bf16_t*)gamma; p.beta = (const bf16_t*)beta;
+  p.rows = M; p.D = K; p.ldx = ldx; p.eps = eps;
+  p.x8 = (uint8_t*)x8; p.exps = exp; p.ld8 = ld8;
+  const dim3 block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (ln_narrow_rows(K, M)) {
+    if (K == 320) MRAG_LAUNCH((layernorm_rows_kernel<8, 5, true>), dim3((unsigned)((M + 31) / 32)), block, 0, s, p);
+    else if (K == 640) MRAG_LAUNCH((layernorm_rows_kernel<16, 5, true>), dim3((unsigned)((M + 15) / 16)), block, 0, s, p);
+    else if (K == 1024) MRAG_LAUNCH((layernorm_rows_kernel<16, 8, true>), dim3((unsigned)((M + 15) / 16)), block, 0, s, p);
+    else MRAG_LAUNCH((layernorm_rows_kernel<32, 5, true>), dim3((unsigned)((M + 7) / 8)), block, 0, s, p);
+  } else if (K <= 1024) {
+    MRAG_LAUNCH((layernorm_kernel<2, true>), dim3((unsigned)((M + 3) / 4)), block, 0, s, p);
+  } else {
+    MRAG_LAUNCH((layernorm_kernel<4, true>), dim3((unsigned)((M + 3) / 4)), block, 0, s, p);
+  }
+  MRAG_LAUNCH_CHECK();
+  (void)__atomic_fetch_add(&g_fp8_k64_launches[1], 1ull, __ATOMIC_RELAXED);
   return MRAG_OK;
 }
 

@@ -26,7 +26,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .layers import CACHE, cat0, conv3x3, conv_t3, host_scalar, lin_w
+from .layers import CACHE, cat0, conv3x3, conv_t3, feed_forward, host_scalar, lin_w
 
 
 class TembBank:
@@ -202,7 +202,7 @@ class BasicTransformerBlock(nn.Module):
         ln = lambda n, v: ops.layernorm(v, n.weight, n.bias, n.eps)
         x = self.attn1(ln(self.norm1, x), None, resid=x, temporal=temporal)                     # :263
         x = self.attn2(ln(self.norm2, x), context, resid=x, temporal=temporal)                  # :264  (context None -> self-attention)
-        return self.ff(ln(self.norm3, x), resid=x)                                              # :265
+        return feed_forward(self.ff, self.norm3, x)                                             # :265  (bf16 unless layers.set_ff_precision marked it)
 
 
 class SpatialTransformer(nn.Module):

@@ -122,6 +122,64 @@ def conv3x3(x: torch.Tensor, conv: nn.Conv2d, *, stride: int = 1, upsample: bool
     return y.view(N, Ho, Wo, cout)
 
 
+FF_SITES_ATTR = "_mrag_ff_fp8_sites"
+FF_SITES = ("ff1", "ff2")
+# The gates of a marked feed-forward, set from the measured table of tools/ff_fp8_measure.py: a site / shape that did not beat its bf16 launch there,
+# or is smaller than anything measured, stays bf16.  Tests of reduced models set all three to 0.
+# Both sites: calls of fewer rows stay bf16.  4 608 rows (DynamiCrafter-1024's middle block, C = 1280) is the smallest problem measured; FF1 wins there (1.33x).
+FF_FP8_MIN_ROWS = 4608
+# The output projection ("ff2") also needs this many rows -- 18 432 x 1280 wins (1.25x), 4 608 x 1280 (90 tiles of the kernel's one 256x256 shape) loses (0.97x) --
+# and this many channels: the row quantiser in front of it (3 bytes per element of the 4 C wide GEGLU output) costs what the kernel saves at C = 640 (1.01x per
+# GEMM, -0.25 ms on the SVD step: a tie) and more at C = 320, where the 256-wide tile also computes 512 columns for 320 (0.72x / 0.68x).
+FF2_FP8_MIN_ROWS = 18432
+FF2_FP8_MIN_WIDTH = 1280
+
+
+def set_ff_precision(module: nn.Module, precision: str = "bf16", sites=FF_SITES) -> nn.Module:
+    """precision of the feed-forward linears of the UNets' transformer blocks under `module` (every dynamicrafter.FeedForward and svd_unet.FeedForward):
+    "bf16" (default, the reference precision) or "fp8" -- the e4m3 GEMM mrag_gemm_fp8_k64 (per-row activation exponents, per-output-channel weight
+    exponents, fp32 accumulation) at the `sites` named: "ff1" the GEGLU projection, fed by a LayerNorm that writes e4m3 (ops.layernorm_e4m3), "ff2" the
+    output projection with its residual, fed by a row quantiser.  Calls of fewer than FF_FP8_MIN_ROWS rows stay bf16, and so does "ff2" below
+    FF2_FP8_MIN_ROWS rows or FF2_FP8_MIN_WIDTH channels: the shapes measured to lose, or smaller than any measured.  Returns the module."""
+    from . import dynamicrafter, svd_unet
+    if precision not in ("bf16", "fp8"):
+        raise ValueError(f"feed-forward precision must be 'bf16' or 'fp8', got {precision!r}")
+    sites = tuple(sites)
+    if not sites or any(s not in FF_SITES for s in sites):
+        raise ValueError(f"feed-forward sites are a non-empty subset of {FF_SITES}, got {sites!r}")
+    for m in module.modules():
+        if isinstance(m, (dynamicrafter.FeedForward, svd_unet.FeedForward)):
+            setattr(m, FF_SITES_ATTR, tuple(s for s in FF_SITES if s in sites) if precision == "fp8" else ())
+    return module
+
+
+def feed_forward(ff: nn.Module, norm: nn.LayerNorm, x: torch.Tensor) -> torch.Tensor:
+    """x + ff(norm(x)) of a pre-norm transformer block for a GEGLU FeedForward (`ff.net`: GEGLU, Dropout, Linear).  Unmarked (the default): the
+    LayerNorm launch and `ff` exactly as the block called them before; marked by `set_ff_precision`: the sites that are on run on the e4m3 GEMM."""
+    pj, out = ff.net[0].proj, ff.net[2]
+    sites = getattr(ff, FF_SITES_ATTR, ())
+    C, inner = pj.weight.shape[1], out.weight.shape[1]
+    rows = x.numel() // C
+    if sites and (rows < FF_FP8_MIN_ROWS or out.weight.shape[0] != C):
+        sites = ()
+    ff1 = "ff1" in sites and ops.fp8_linear_k64_supported(2 * inner, C, ops.EPI_GEGLU)
+    ff2 = "ff2" in sites and rows >= FF2_FP8_MIN_ROWS and C >= FF2_FP8_MIN_WIDTH and ops.fp8_linear_k64_supported(C, inner, ops.EPI_RESID)
+    if not (ff1 or ff2):
+        return ff(ops.layernorm(x, norm.weight, norm.bias, norm.eps), resid=x)
+    w, b = CACHE.get(("geglu", id(pj)), (pj.weight, pj.bias), lambda: ops.geglu_interleave(pj.weight, pj.bias))
+    if ff1:
+        # the weights quantised once per output channel (FF1: the interleaved rows), the activation by the LayerNorm itself
+        w8, w_exp = CACHE.get(("geglu8", id(pj)), (pj.weight, pj.bias), lambda: ops.quant_rows_e4m3(bf16(w)))
+        h = ops.linear_fp8_k64(ops.layernorm_e4m3(x, norm.weight, norm.bias, norm.eps), w8, w_exp, b, epilogue=ops.EPI_GEGLU)
+        h = h.view(*x.shape[:-1], inner)
+    else:
+        h = ops.linear(ops.layernorm(x, norm.weight, norm.bias, norm.eps), w, b, epilogue=ops.EPI_GEGLU)
+    if ff2:
+        w8, w_exp = CACHE.get(("ff2w8", id(out)), out.weight, lambda: ops.quant_rows_e4m3(bf16(out.weight)))
+        return ops.linear_fp8_k64(h, w8, w_exp, out.bias, epilogue=ops.EPI_RESID, resid=x)
+    return ops.linear(h, out.weight, out.bias, epilogue=ops.EPI_RESID, resid=x)
+
+
 def conv_t3(x: torch.Tensor, conv: nn.Conv3d, B: int, T: int, *, resid: Optional[torch.Tensor] = None, acc_scale: float = 1.0) -> torch.Tensor:
     """nn.Conv3d((3,1,1), padding (1,0,0)) on x [(b t), HW, C]; with `resid`: resid + acc_scale * conv(x)"""
     C = x.shape[-1]

@@ -535,6 +535,97 @@ def linear_fp8(x: torch.Tensor, w8: torch.Tensor, w_exp: torch.Tensor, bias: Opt
     return out
 
 
+def fp8_k64_launch_counts() -> dict:
+    """launches of the feed-forward fp8 path's two entry points so far (mrag_gemm_fp8_k64_launch_counts): {"gemm": n, "ln": n}"""
+    buf = (ctypes.c_uint64 * 2)()
+    _lib.lib().mrag_gemm_fp8_k64_launch_counts(buf, 2)
+    return {"gemm": int(buf[0]), "ln": int(buf[1])}
+
+
+def fp8_linear_k64_supported(N: int, K: int, epilogue: int = EPI_NONE) -> bool:
+    """shapes and epilogues mrag_gemm_fp8_k64 takes (include/mrag_hip.h): K % 64 == 0, N % 16 == 0 (EPI_GEGLU: N % 32 == 0) with EPI_NONE, EPI_RESID
+    or EPI_GEGLU; any row count"""
+    if epilogue not in (EPI_NONE, EPI_RESID, EPI_GEGLU):
+        return False
+    return N > 0 and K > 0 and K % 64 == 0 and N % (32 if epilogue == EPI_GEGLU else 16) == 0
+
+
+def _fp8_rows_workspace(device: torch.device, M: int, K: int, kind: str):
+    """(x8 [M, K] uint8, exp [M] int32) inside the grow-only workspace `kind` of the (device, stream)"""
+    exp_bytes = (M * 4 + 255) // 256 * 256
+    ws = _attn_workspace(device, exp_bytes + M * K, kind)
+    return ws[exp_bytes:exp_bytes + M * K].view(M, K), ws[:M * 4].view(torch.int32)
+
+
+def layernorm_e4m3(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], eps: float):
+    """quant_rows_e4m3(layernorm(x, weight, bias, eps)) bit for bit, in one pass over x (mrag_layernorm_e4m3): the bf16 rows are never written.
+    Returns (x8 [M, K] uint8, exp [M] int32) inside a grow-only workspace of the (device, stream) -- valid until the next call on that stream, which
+    is what a GEMM launched behind it on the stream needs.  Rows the kernel does not take (MRAG_ENOTSUP) go through the two launches."""
+    _dev(x, name="x")
+    x2 = _rows(x)
+    M, K = x2.shape
+    if K % 16 != 0:
+        raise ValueError(f"layernorm_e4m3: K % 16 == 0 (the e4m3 rows are written 16 bytes at a time), got K={K}")
+    x8, ex = _fp8_rows_workspace(x.device, M, K, "fp8ln")
+    rc = _lib.lib().mrag_layernorm_e4m3(_stream(), _p(x2), _p(weight), _p(bias), eps, _p(x8), _p(ex), M, K, x2.stride(0), x8.stride(0))
+    if rc == _lib.MRAG_ENOTSUP:
+        return quant_rows_e4m3(layernorm(x2, weight, bias, eps), out=(x8, ex))
+    check(rc, "mrag_layernorm_e4m3")
+    return x8, ex
+
+
+def linear_fp8_k64(x, w8: torch.Tensor, w_exp: torch.Tensor, bias: Optional[torch.Tensor] = None, *, epilogue: int = EPI_NONE,
+                   resid: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`linear_fp8` for the UNets' feed-forward shapes (mrag_gemm_fp8_k64): K % 64 == 0, epilogues EPI_NONE / EPI_RESID (out may be resid) / EPI_GEGLU
+    (w8, w_exp and bias in `geglu_interleave`'s row order; out [M, N / 2]).  `x` is bf16 rows [..., K], quantised per row in front of the launch into a
+    grow-only workspace, or an already quantised pair (x8 [M, K] uint8, exp [M] int32) such as `layernorm_e4m3` returns (out is then [M, n]).
+    Nothing read back: capturable into a HIP graph.  Raises on what the kernel does not take (`fp8_linear_k64_supported`)."""
+    _dev(w8, torch.uint8, "w8"); _dev(w_exp, torch.int32, "w_exp")
+    if bias is not None:
+        _dev(bias, name="bias")
+    if isinstance(x, (tuple, list)):
+        a8, a_exp = x
+        _dev(a8, torch.uint8, "x8"); _dev(a_exp, torch.int32, "exp")
+        if a8.dim() != 2 or a8.stride(1) != 1 or tuple(a_exp.shape) != (a8.shape[0],) or not a_exp.is_contiguous():
+            raise ValueError("linear_fp8_k64: a quantised x is (x8 [M, K] uint8 with contiguous rows, exp [M] int32)")
+        lead = (a8.shape[0],)
+        M, K = a8.shape
+    else:
+        _dev(x, name="x")
+        x2 = _rows(x)
+        lead = tuple(x.shape[:-1])
+        M, K = x2.shape
+    N = w8.shape[0]
+    if w8.dim() != 2 or w8.shape[1] != K or w8.stride(1) != 1 or tuple(w_exp.shape) != (N,) or not w_exp.is_contiguous():
+        raise ValueError(f"linear_fp8_k64: w8 {tuple(w8.shape)} / w_exp {tuple(w_exp.shape)} do not match K={K}")
+    if not fp8_linear_k64_supported(N, K, epilogue):
+        raise ValueError(f"linear_fp8_k64: N={N}, K={K}, epilogue {epilogue} outside the kernel's shapes (K % 64 == 0, N % 16 == 0, GEGLU N % 32 == 0; "
+                         "EPI_NONE / EPI_RESID / EPI_GEGLU)")
+    if (epilogue == EPI_RESID) != (resid is not None):
+        raise ValueError("linear_fp8_k64: resid goes with EPI_RESID")
+    if not isinstance(x, (tuple, list)):
+        a8, a_exp = _fp8_rows_workspace(x.device, M, K, "fp8k64")
+        quant_rows_e4m3(x2, out=(a8, a_exp))
+    ncols = N // 2 if epilogue == EPI_GEGLU else N
+    if out is None:
+        out = torch.empty(*lead, ncols, dtype=torch.bfloat16, device=w8.device)
+    o2 = _rows(_dev(out, name="out"))
+    if tuple(o2.shape) != (M, ncols):
+        raise ValueError(f"linear_fp8_k64: out {tuple(out.shape)} is not [{M}, {ncols}]")
+    a = GemmFp8Args()
+    a.A8, a.W8, a.a_exp, a.w_exp, a.bias, a.C = _p(a8), _p(w8), _p(a_exp), _p(w_exp), _p(bias), _p(o2)
+    a.M, a.N, a.K = M, N, K
+    a.lda, a.ldw, a.ldc = a8.stride(0), w8.stride(0), o2.stride(0)
+    a.epilogue = epilogue
+    if resid is not None:
+        r2 = _rows(_dev(resid, name="resid"))
+        if tuple(r2.shape) != (M, N):
+            raise ValueError(f"linear_fp8_k64: resid {tuple(resid.shape)} is not [{M}, {N}]")
+        a.resid, a.ldr = _p(r2), r2.stride(0)
+    check(_lib.lib().mrag_gemm_fp8_k64(_stream(), ctypes.byref(a)), "mrag_gemm_fp8_k64")
+    return out
+
+
 def timestep_embedding(t: torch.Tensor, dim: int) -> torch.Tensor:
     _dev(t, torch.float32, "t")
     out = torch.empty(t.shape[0], dim, dtype=torch.bfloat16, device=t.device)

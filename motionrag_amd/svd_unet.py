@@ -23,7 +23,7 @@ from torch import nn
 from . import ops
 from .attn_processor import Attention
 from .dynamicrafter import TembBank, temb_proj
-from .layers import CACHE, cat0, conv3x3, conv_t3, host_scalar
+from .layers import CACHE, cat0, conv3x3, conv_t3, feed_forward, host_scalar
 
 
 def _ln(n: nn.LayerNorm, x):
@@ -210,7 +210,7 @@ class BasicTransformerBlock(nn.Module):
     def forward(self, x, encoder_hidden_states):
         x = _attn_plus(self.attn1, _ln(self.norm1, x), x)
         x = _attn_plus(self.attn2, _ln(self.norm2, x), x, encoder_hidden_states=encoder_hidden_states)
-        return self.ff(_ln(self.norm3, x), resid=x)
+        return feed_forward(self.ff, self.norm3, x)                                    # bf16 unless layers.set_ff_precision marked it
 
 
 class TemporalBasicTransformerBlock(nn.Module):
@@ -230,7 +230,7 @@ class TemporalBasicTransformerBlock(nn.Module):
     def forward(self, x, temporal, first_frame_context):
         """x [(b f), HW, C] in place of the package's [(b hw), f, C]; first_frame_context [b, 1, D]"""
         b, f, hw = temporal
-        x = self.ff_in(_ln(self.norm_in, x), resid=x)
+        x = feed_forward(self.ff_in, self.norm_in, x)
         x = _attn_plus(self.attn1, _ln(self.norm1, x), x, temporal=temporal)
         # attn2: every (b, hw) row attends to ONE context token, so softmax == 1 exactly and the branch is
         # to_out(to_v(context)) whatever the query; the package builds `time_context` with rows ordered (hw, b) while the
@@ -242,7 +242,7 @@ class TemporalBasicTransformerBlock(nn.Module):
         a = self.attn2
         vec = ops.linear(ops.linear(first_frame_context.reshape(b, -1).contiguous(), a.to_v.weight), a.to_out[0].weight, a.to_out[0].bias)   # [b, C]
         x = ops.add_bcast(x, vec, 1)                                                   # row r -> vec[r % b]; ((b f) hw + s) % b == (b hw + s) % b
-        return self.ff(_ln(self.norm3, x), resid=x)
+        return feed_forward(self.ff, self.norm3, x)                                    # bf16 unless layers.set_ff_precision marked it
 
 
 class TransformerSpatioTemporalModel(nn.Module):
