@@ -603,7 +603,13 @@ int mrag_cfg_dpm_step_bf16(void* stream, const void* v_pred, void* latents, void
 /*       (q - x)^2) and re-ranks them: the distances returned are order 1's bit  */
 /*       for bit, whatever the call shape (round 6; mode 2 of the oracle restates */
 /*       selection + second scoring).  "dot": 1 - chain, no second scoring.       */
-/*       n_queries >= 16, k <= 16, else MRAG_ENOTSUP;                            */
+/*       n_queries >= 16, k <= 32, else MRAG_ENOTSUP.  17 <= k <= 32 (the WIDE     */
+/*       lists) is taken only when `order` names the form (2, 3 or 4), never by  */
+/*       order 0: "l2" then selects the k nearest under the first score, scores  */
+/*       those k again and re-ranks them (the oracle's keep = max(16, k)); the   */
+/*       kernels carry 32-deep lists and the streaming form's workgroups cover   */
+/*       at most 128 queries.  The workspace is sized by                          */
+/*       mrag_topk_workspace_bytes_k(n_rows, n_queries, k).                       */
 /*       Tables of one resident round of workgroups (10 000 x 256: BASELINE config #1) run it as ONE launch: the first scores of every (query,
  *       row) leave as a dense matrix in the workspace, every workgroup waits -- bounded -- until the grid has arrived, and the workgroups then
  *       finish the queries (16 nearest under the first score, second scoring, filter order).  Tables up to 65 536 rows / 64 MB of first scores
@@ -612,19 +618,23 @@ int mrag_cfg_dpm_step_bf16(void* stream, const void* v_pred, void* latents, void
  *   3 = order 2, streaming (three-launch) form forced;   4 = order 2, one-launch form forced (MRAG_ENOTSUP where its plan does not apply) and
  *       WITHOUT waiting: every workgroup but the last arriver leaves at once and the last one finishes every query -- diagnostics of the two forms'
  *       equality and of the bounded wait's fall-back.                                                                                             */
-/*   0 = automatic: 2 where it applies (faster at every table size measured,     */
-/*       1 000 to 10^6 rows), else 1.  "l2": a row gets the same distance from   */
+/*   0 = automatic: 2 where it applies with k <= 16 (faster at every table size  */
+/*       measured, 1 000 to 10^6 rows), else 1 (k > 16 always: the wide lists    */
+/*       return other rows at the list's edge, so they are opt-in).  "l2": a row gets the same distance from   */
 /*       both; WHICH rows make the list can differ only where the k-th and a     */
 /*       later candidate are closer than the expansion's error AND the later one */
 /*       ranks beyond 16 under it.  "dot": the two orders may differ in the last */
 /*       bits of a distance (never in a rank whose gap exceeds the fp32 rounding */
 /*       of the sum: tests compare both with the float64 oracle).                */
 /* ------------------------------------------------------------------------ */
-/* workspace: >= mrag_topk_workspace_bytes, 16-byte aligned.  Its first 64 bytes are arrival counters of the single-launch forms
+/* workspace: >= mrag_topk_workspace_bytes (orders 2 - 4 with 17 <= k <= 32: >= mrag_topk_workspace_bytes_k), 16-byte aligned.  Its first 64 bytes are arrival counters of the single-launch forms
  * (n_queries <= 4: scan + merge in ONE launch, the last workgroup to arrive merges; the one-launch fan-out form: words 8..14, two
  * counter sets used alternately): they must be ZERO before the first call on a workspace; every call leaves them ready for the next one
  * (of any form, on the same stream), so a workspace is zeroed once when it is allocated and never written by the caller afterwards.   */
 int64_t mrag_topk_workspace_bytes(int64_t n_rows, int32_t n_queries);
+/* the same for a call at list length k: equal to mrag_topk_workspace_bytes for k <= 16, never smaller than it above (the 32-deep per-workgroup lists
+ * of the streaming fan-out form).  mrag_topk_f32 checks `workspace_bytes` against this value when `order` is 2, 3 or 4 and k > 16.               */
+int64_t mrag_topk_workspace_bytes_k(int64_t n_rows, int32_t n_queries, int32_t k);
 int mrag_topk_f32(void* stream, const float* db, const int32_t* group, int64_t n_rows, int32_t dim,
                   const float* queries, const int32_t* exclude, int32_t n_queries,
                   int32_t k, int32_t metric,

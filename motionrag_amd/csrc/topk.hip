@@ -25,8 +25,12 @@ namespace {
 constexpr int ROWS = 256;      // rows per workgroup iteration (4 waves x 64 lanes)
 
 // the fan-out plan: queries per workgroup (32 TN), parts (workgroups along the table), rows per part
+// `list` = the per-query list depth of the kernels: 16 (k <= 16), or 32 (the wide lists, 17 <= k <= 32).  At depth 32 the 256-query workgroup does not fit the CU's
+// 160 KB of LDS (98 304 of ring + 256 x 42 x 8 = 184 320 bytes), so the wide plan's tile stops at TN = 4 (128 queries: 141 312 bytes); per_cu, parts and WN follow
+// from the wide LDS size, and the wide workgroup is always four waves: the eight-wave 128-query kernel (2 tiles x 2 query groups, 256 registers per lane) spilled 8 - 12
+// registers of the 32-deep insertion chain to scratch and is not built.  Nothing in the plan depends on `list` at depth 16.
 struct MfmaPlan { int TN, WN, QB, RB, gy, parts, rows_per_part; size_t lds, bytes; };
-inline MfmaPlan plan_mfma(long long n_rows, int nq) {
+inline MfmaPlan plan_mfma(long long n_rows, int nq, int list = 16) {
   MfmaPlan pl;
   const int qtiles = (nq + 31) / 32;
   pl.RB = 128;
@@ -37,29 +41,33 @@ inline MfmaPlan plan_mfma(long long n_rows, int nq) {
   // 20 000 rows: 221 / 225 / 231 / 190; profiles/r5_topk_query_tile_by_table_size.txt).  A larger table streams: the widest tile the batch fills (one pass
   // over the table per 256 queries).
   int widest = 1;
-  for (int t = 8; t >= 1; t >>= 1)
+  for (int t = list > 16 ? 4 : 8; t >= 1; t >>= 1)
     if (t <= qtiles) { widest = t; break; }
   pl.TN = widest;
   for (int t = 1; t <= widest; t <<= 1)
     if (blocks * ((qtiles + t - 1) / t) <= (t == 1 ? 512 : 256)) { pl.TN = t; break; }
   pl.QB = 32 * pl.TN;
-  pl.lds = (size_t)mfma_stages(pl.TN) * (pl.RB + pl.QB) * 128 + (size_t)pl.QB * (17 + 8 + 1) * sizeof(Cand) + 4 * 32 * sizeof(float);
+  pl.lds = (size_t)mfma_stages(pl.TN) * (pl.RB + pl.QB) * 128 + (size_t)pl.QB * (list + 1 + 8 + 1) * sizeof(Cand) + 4 * 32 * sizeof(float);
   pl.gy = (nq + pl.QB - 1) / pl.QB;
   int per_cu = (int)((160 * 1024) / pl.lds);
-  per_cu = per_cu < 1 ? 1 : per_cu > 2 ? 2 : per_cu;                  // (160-208 VGPRs at TN <= 2: two workgroups per CU)
+  per_cu = per_cu < 1 ? 1 : per_cu > 2 ? 2 : per_cu;                  // (160-208 VGPRs at TN <= 2: two workgroups per CU; depth 32: 284 at TN = 1, where a grid of two per CU runs its second half as a second round)
   long long parts = (256LL * per_cu + pl.gy - 1) / pl.gy;
   parts = parts < 1 ? 1 : parts > blocks ? blocks : parts;
   const long long bpp = (blocks + parts - 1) / parts;
   pl.parts = (int)((blocks + bpp - 1) / bpp);
   // waves: the 256-query workgroup is eight waves (two query groups of four tiles); so is the 128-query workgroup of a ONE-row-block plan (two groups of two tiles):
   // its 64 MFMAs per slab and wave were the long pole of a 10 000-row search (42 us on 158 workgroups), and two waves per SIMD halve them
-  pl.WN = (pl.TN == 8 || (pl.TN == 4 && bpp == 1)) ? 2 : 1;
+  pl.WN = list > 16 ? 1 : (pl.TN == 8 || (pl.TN == 4 && bpp == 1)) ? 2 : 1;
   pl.rows_per_part = (int)(bpp * pl.RB);
-  pl.bytes = 2 * (((size_t)nq * sizeof(float) + 255) / 256 * 256) + (size_t)nq * pl.parts * 16 * sizeof(Cand);   // |q|^2, shared thresholds, per-workgroup lists
+  pl.bytes = 2 * (((size_t)nq * sizeof(float) + 255) / 256 * 256) + (size_t)nq * pl.parts * list * sizeof(Cand);   // |q|^2, shared thresholds, per-workgroup lists
   return pl;
 }
 
 inline bool mfma_applies(int nq, int k, int dim) { return nq >= 16 && k <= 16 && dim % 4 == 0; }
+// the wide lists (17 <= k <= 32): only for a caller that names the fan-out form (order 2 - 4).  They select other rows than the scan form at the list's edge,
+// so `order = 0` never takes them (mfma_auto below)
+inline bool mfma_applies_wide(int nq, int k, int dim) { return nq >= 16 && k > 16 && k <= 32 && dim % 4 == 0; }
+inline int mfma_list(int k) { return k > 16 ? 32 : 16; }
 
 // the plan of the dense forms: `ok` = the first scores fit the workspace (<= 65 536 rows, <= 64 MB); `resident` = a tile exists whose whole grid is on the chip at
 // once -> ONE launch with the grid wait (checked against the runtime's occupancy at launch); otherwise TWO launches: the same kernel without the wait, then
@@ -139,15 +147,24 @@ void plan(long long n_rows, int nq, int* slices, int* rows_per_slice) {
 
 constexpr int64_t kTicketBytes = 64;     // arrival counters of the fused single-launch form (<= 4 queries = 1 query tile ... 4 tiles of QT = 1)
 
-extern "C" int64_t mrag_topk_workspace_bytes(int64_t n_rows, int32_t n_queries) {
+static int64_t topk_workspace_need(int64_t n_rows, int32_t n_queries, int list) {
   if (n_rows <= 0 || n_queries <= 0) return 0;
   int slices, rps;
   plan(n_rows, n_queries, &slices, &rps);
   const int64_t scan = kTicketBytes + (int64_t)n_queries * slices * 4 * 64 * (int64_t)sizeof(Cand);
-  const int64_t fan = n_queries >= 16 ? kTicketBytes + (int64_t)plan_mfma(n_rows, n_queries).bytes : 0;   // either form fits (the `order` argument picks one)
+  const int64_t fan = n_queries >= 16 ? kTicketBytes + (int64_t)plan_mfma(n_rows, n_queries, list).bytes : 0;   // either form fits (the `order` argument picks one)
   const int64_t dense = n_queries >= 16 ? kTicketBytes + (int64_t)plan_dense(n_rows, n_queries).bytes : 0;  // (0 bytes when the one-launch plan does not apply)
   const int64_t m = scan > fan ? scan : fan;
   return m > dense ? m : dense;
+}
+
+extern "C" int64_t mrag_topk_workspace_bytes(int64_t n_rows, int32_t n_queries) { return topk_workspace_need(n_rows, n_queries, 16); }
+
+extern "C" int64_t mrag_topk_workspace_bytes_k(int64_t n_rows, int32_t n_queries, int32_t k) {
+  const int64_t base = topk_workspace_need(n_rows, n_queries, 16);
+  if (k <= 16) return base;
+  const int64_t wide = topk_workspace_need(n_rows, n_queries, 32);          // (the wide plan has other tiles and parts: never report less than the plain need)
+  return wide > base ? wide : base;
 }
 
 extern "C" int mrag_topk_f32(void* stream, const float* db, const int32_t* group, int64_t n_rows, int32_t dim, const float* queries,
@@ -160,7 +177,9 @@ extern "C" int mrag_topk_f32(void* stream, const float* db, const int32_t* group
   if (metric != 0 && metric != 1) return MRAG_EINVAL;
   if (exclude && !group) return MRAG_EINVAL;
   if (((uintptr_t)db | (uintptr_t)queries) & 15) return MRAG_EINVAL;
-  if (workspace_bytes < mrag_topk_workspace_bytes(n_rows, n_queries)) return MRAG_EINVAL;
+  // (the need of THIS call: the wide lists' where the caller names the fan-out form at k > 16; the plain need for k <= 16 and for orders 0 / 1, whose callers size by mrag_topk_workspace_bytes)
+  const bool wide = order >= 2 && order <= 4 && k > 16 && k <= 32;
+  if (workspace_bytes < (wide ? mrag_topk_workspace_bytes_k(n_rows, n_queries, k) : mrag_topk_workspace_bytes(n_rows, n_queries))) return MRAG_EINVAL;
   TopkP p{};
   if (postfilter != 0 && postfilter != 1) return MRAG_EINVAL;
   const bool post = postfilter && exclude;
@@ -172,7 +191,8 @@ extern "C" int mrag_topk_f32(void* stream, const float* db, const int32_t* group
   const bool small = small_db(n_rows, n_queries);
   hipStream_t s = (hipStream_t)stream;
   if (order < 0 || order > 4) return MRAG_EINVAL;
-  if (order >= 2 && !mfma_applies(n_queries, k, dim)) return MRAG_ENOTSUP;
+  if (order >= 2 && !mfma_applies(n_queries, k, dim) && !mfma_applies_wide(n_queries, k, dim)) return MRAG_ENOTSUP;
+  const int list = mfma_list(k);                          // (32 only behind order >= 2: mfma_auto refuses k > 16)
   if (order >= 2 || (order == 0 && mfma_auto(n_rows, n_queries, k, dim))) {
     // ---- the fan-out form in ONE launch: tables whose grid is resident at once (order 3 = never, order 4 = this form without waiting: diagnostics)
     if (order != 3) {
@@ -185,25 +205,25 @@ extern "C" int mrag_topk_f32(void* stream, const float* db, const int32_t* group
         d.ld = dp.ld; d.total = dp.resident ? dp.parts * dp.gy : 0;
         d.spin_limit = order == 4 ? 0 : 40000;                // x ~1 us of s_sleep: a workgroup that has not seen the grid arrive by then leaves (the last arriver finishes alone)
         d.mp = p; d.mp.rescore = metric == 0 ? 1 : 0;
-        return launch_topk_dense(s, d, metric, dp.TN, dp.WN, dp.QB, dim3(dp.parts, dp.gy), dp.lds, order == 4);
+        return launch_topk_dense(s, d, metric, dp.TN, dp.WN, dp.QB, list, dim3(dp.parts, dp.gy), dp.lds, order == 4);
       }
       if (order == 4) return MRAG_ENOTSUP;
     }
     // ---- the fan-out form: one fp32 MFMA pass over the table per 256 queries
-    const MfmaPlan pl = plan_mfma(n_rows, n_queries);
+    const MfmaPlan pl = plan_mfma(n_rows, n_queries, list);
     TopkMP m{};
     m.db = db; m.group = p.group; m.q = queries; m.excl = exclude; m.n_rows = n_rows; m.dim = dim; m.nq = n_queries;
-    m.k = metric == 0 ? 16 : k;      // "l2": the second scoring takes the 16 nearest under the first score, so the lists (and their thresholds) are 16 deep
+    m.k = metric == 0 && k < 16 ? 16 : k;      // "l2": the second scoring takes the max(16, k) nearest under the first score, so the lists (and their thresholds) are that deep
     m.nparts = pl.parts; m.rows_per_part = pl.rows_per_part; m.nslab = (dim + 31) / 32;
     const size_t qbytes = ((size_t)n_queries * sizeof(float) + 255) / 256 * 256;
     m.qq = (float*)((char*)workspace + kTicketBytes);
     m.tau_g = (unsigned*)((char*)workspace + kTicketBytes + qbytes);
     m.lists = (Cand*)((char*)workspace + kTicketBytes + 2 * qbytes);
-    int rc = launch_topk_mfma(s, m, metric, pl.TN, pl.WN, dim3(pl.parts, pl.gy), pl.lds);   // (|q|^2 pre-pass, then the fan-out kernel)
+    int rc = launch_topk_mfma(s, m, metric, pl.TN, pl.WN, list, dim3(pl.parts, pl.gy), pl.lds);   // (|q|^2 pre-pass, then the fan-out kernel)
     if (rc != MRAG_OK) return rc;
     MRAG_COUNT(MRAG_K_TOPK_MFMA);
     p.ws = m.lists; p.slices = pl.parts; p.wpb = 1; p.rescore = metric == 0 ? 1 : 0;
-    rc = launch_topk_merge(s, p, 16);
+    rc = launch_topk_merge(s, p, list);
     if (rc != MRAG_OK) return rc;
     MRAG_COUNT(MRAG_K_TOPK_MERGE);
     return MRAG_OK;

@@ -94,14 +94,21 @@ struct TopkP {
   const int* post_group;  // postfilter: group ids consulted AFTER selection (then `group` above is null and the scan excludes nothing)
   unsigned* tickets;    // FUSED: one arrival counter per query tile (zero between calls)
   int wpb;              // waves per workgroup: always 4 (small databases spread by giving each WAVE 16 rows instead of 64: small_db())
-  int rescore;          // merge (LIST = 16, metric l2 of the fan-out form): the 16 nearest candidates are re-scored with the direct sum of (q - x)^2 and re-ranked
+  int rescore;          // merge (LIST = 16 / 32, metric l2 of the fan-out form): the nearest candidates (16; max(16, k) at depth 32) are re-scored with the direct sum of (q - x)^2 and re-ranked
 };
+
+// candidates the first score selects for query lists of compile-time depth DEPTH (16: k <= 16; 32: the wide lists, 17 <= k <= 32) -- oracle/topk_oracle.c's `keep`
+template <int DEPTH>
+__device__ __forceinline__ int topk_keep(const TopkP& p) {
+  if constexpr (DEPTH > 16) return p.rescore ? (p.k > 16 ? p.k : 16) : p.k;
+  else return p.rescore ? 16 : p.k;
+}
 
 // the streaming fan-out form (topk_mfma.hip)
 struct TopkMP {
   const float* db; const int* group; const float* q; const int* excl; const float* qq;
   unsigned* tau_g;        // [nq] the best k-th distance any workgroup has published for the query, as an order-preserving unsigned key (atomicMin)
-  Cand* lists;
+  Cand* lists;            // [nq][nparts][LIST]: LIST = the kernel's list depth (16 or 32)
   long long n_rows; int dim, nq, k, nparts, rows_per_part, nslab;
 };
 
@@ -165,11 +172,13 @@ __device__ __forceinline__ float chain16_fold(float acc) {
 // whose minimum does not exceed it can contribute (about k of thousands).  Phase B merges just those.  The result is the
 // unique top-k under the total order (distance, row), whatever the merge order.
 // `sh` = 4 x 64 candidates + 1 of LDS scratch.
-// LIST = entries per partial list: 64 (the scan kernel's per-wave lists) or 16 (the fan-out kernel's per-workgroup lists; lanes >= 16 read +inf)
+// LIST = entries per partial list: 64 (the scan kernel's per-wave lists) or 16 / 32 (the fan-out kernel's per-workgroup lists; lanes >= LIST read +inf)
 // the tail of every merge: `run` = the sorted nearest candidates of query q across the lanes of the group's first wave (lt < 64) -> second scoring
 // (p.rescore), filter order, output.  lt = thread index inside the 256-thread group that merges this query (the merge kernels: threadIdx.x; the
 // one-launch fan-out form runs two groups per 512-thread workgroup), sh = the group's 257-candidate scratch, store = false: a group without a
-// query of its own walks through the barriers only.
+// query of its own walks through the barriers only.  DEPTH = 16, or 32 for the wide lists (17 <= k <= 32): the second scoring then takes the max(16, k)
+// nearest in DEPTH / 16 passes of the group.
+template <int DEPTH = 16>
 __device__ __forceinline__ void finish_query(const TopkP& p, const int q, Cand run, Cand* sh, const int lt, const bool store) {
   const int lane = lt & 63, wave = lt >> 6;
   Cand inf; inf.d = INFINITY; inf.r = INT_MAX;
@@ -179,27 +188,38 @@ __device__ __forceinline__ void finish_query(const TopkP& p, const int q, Cand r
     // feeds condition_fusion's weights (src/projects/condition/utils.py:7-36).  So the 16 nearest candidates under that score are scored
     // AGAIN here with the scan kernel's definition -- the direct sum of (q - x)^2 on 16 interleaved fmaf chains + the fixed tree, oracle mode 0 -- and
     // re-ranked: the distances a row gets no longer depend on the call shape, and ranks among near neighbours follow the exact form.  16 lanes per
-    // candidate, 16 candidates per pass of the group.
+    // candidate, 16 candidates per pass of the group.  (DEPTH = 32: the first keep = max(16, k) lanes are the candidates -- a 22nd nearest under the first
+    // score must not enter a list of 21 through the second --, two passes.)
     __syncthreads();
-    if (wave == 0) sh[lane] = run;
+    if (wave == 0) {
+      if constexpr (DEPTH > 16) sh[lane] = lane < topk_keep<DEPTH>(p) ? run : inf;
+      else sh[lane] = run;
+    }
     __syncthreads();
-    const int c = lt >> 4, s16 = lt & 15;                   // (256 threads: c < 16)
-    const Cand cc = sh[c];
-    float acc = 0.f;
-    if (cc.r != INT_MAX) acc = chain16_partial<0>(p.db + (long long)cc.r * p.dim, p.q + (long long)q * p.dim, p.dim, s16);
-    acc = chain16_fold(acc);
+    const int s16 = lt & 15;
+    Cand cc[DEPTH / 16];
+    float acc[DEPTH / 16];
+#pragma unroll
+    for (int ps = 0; ps < DEPTH / 16; ++ps) {
+      cc[ps] = sh[16 * ps + (lt >> 4)];                     // (256 threads: 16 candidates per pass)
+      acc[ps] = 0.f;
+      if (cc[ps].r != INT_MAX) acc[ps] = chain16_partial<0>(p.db + (long long)cc[ps].r * p.dim, p.q + (long long)q * p.dim, p.dim, s16);
+      acc[ps] = chain16_fold(acc[ps]);
+    }
     __syncthreads();
-    if (s16 == 0 && cc.r != INT_MAX) sh[c].d = acc;
+#pragma unroll
+    for (int ps = 0; ps < DEPTH / 16; ++ps)
+      if (s16 == 0 && cc[ps].r != INT_MAX) sh[16 * ps + (lt >> 4)].d = acc[ps];
     __syncthreads();
-    if (wave == 0) {                                        // re-rank the (up to) 16 by counting: sh[0..15] -> sh[64..79]
-      const Cand c = lane < 16 ? sh[lane] : inf;
+    if (wave == 0) {                                        // re-rank the (up to) DEPTH by counting: sh[0..DEPTH - 1] -> sh[64..64 + DEPTH - 1]
+      const Cand c = lane < DEPTH ? sh[lane] : inf;
       const bool have = c.r != INT_MAX;
-      const int rank = cand_rank(c, 16);
-      if (lane < 16) sh[64 + lane] = inf;
+      const int rank = cand_rank(c, DEPTH);
+      if (lane < DEPTH) sh[64 + lane] = inf;
       __builtin_amdgcn_wave_barrier();
       if (have) sh[64 + rank] = c;
       __builtin_amdgcn_wave_barrier();
-      run = lane < 16 ? sh[64 + lane] : inf;
+      run = lane < DEPTH ? sh[64 + lane] : inf;
     }
   }
   if (wave == 0 && store) {
@@ -245,7 +265,7 @@ __device__ __forceinline__ void merge_query(const TopkP& p, int q, Cand* sh) {
   __syncthreads();
   if (wave == 0) {
     for (int w = 1; w < nw; ++w) best = wave_merge_top(best, sh[w * 64 + lane], lane);
-    if (lane == (p.rescore ? 16 : p.k) - 1) *thr_s = best;   // k-th smallest minimum (the 16th when a second scoring follows: it takes the 16 nearest)
+    if (lane == topk_keep<(LIST == 32 ? 32 : 16)>(p) - 1) *thr_s = best;   // k-th smallest minimum (the 16th -- max(16, k)-th at LIST = 32 -- when a second scoring follows: it takes that many nearest)
   }
   __syncthreads();
   const Cand thr = *thr_s;
@@ -266,7 +286,7 @@ __device__ __forceinline__ void merge_query(const TopkP& p, int q, Cand* sh) {
   __syncthreads();
   if (wave == 0)
     for (int w = 1; w < nw; ++w) run = wave_merge_top(run, sh[w * 64 + lane], lane);
-  finish_query(p, q, run, sh, tid, true);
+  finish_query<(LIST == 32 ? 32 : 16)>(p, q, run, sh, tid, true);
 }
 
 // ---- what the fan-out kernels (topk_mfma.hip, topk_dense.hip) share
@@ -280,11 +300,11 @@ constexpr int dense_stages(int tiles) { return tiles == 1 ? 2 : 3; }   // 32 que
 
 // The family launchers, one per unit (MRAG_FAMILY_LAUNCHER, common.h).  Each looks its kernel up by the template arguments and returns MRAG_ENOTSUP when
 // no instantiation matches, else the status of its launches.
-// topk_scan.hip: topk_scan_kernel<metric, qt, jc> (fused: <.., true, small ? 4 : 16>); topk_merge_kernel<list>, list = 64 or 16
+// topk_scan.hip: topk_scan_kernel<metric, qt, jc> (fused: <.., true, small ? 4 : 16>); topk_merge_kernel<list>, list = 64, 16 or 32
 MRAG_FAMILY_LAUNCHER launch_topk_scan(hipStream_t s, const TopkP& p, int qt, int jc, bool fused, bool small, dim3 grid, size_t lds);
 MRAG_FAMILY_LAUNCHER launch_topk_merge(hipStream_t s, const TopkP& p, int list);
-// topk_mfma.hip: topk_qq_kernel, then topk_mfma_kernel<metric, tn / wn, wn> (tn = 32-query tiles per workgroup)
-MRAG_FAMILY_LAUNCHER launch_topk_mfma(hipStream_t s, const TopkMP& m, int metric, int tn, int wn, dim3 grid, size_t lds);
+// topk_mfma.hip: topk_qq_kernel, then topk_mfma_kernel<metric, tn / wn, wn, list> (tn = 32-query tiles per workgroup; list = 16, or 32 with tn <= 4 and wn = 1)
+MRAG_FAMILY_LAUNCHER launch_topk_mfma(hipStream_t s, const TopkMP& m, int metric, int tn, int wn, int list, dim3 grid, size_t lds);
 // topk_dense.hip: topk_dense_kernel<metric, tn, wn, qbu> and, when the grid is not resident at once (or d.total is 0), topk_dense_finish_kernel;
-// resident_only: MRAG_ENOTSUP instead of the two-launch form
-MRAG_FAMILY_LAUNCHER launch_topk_dense(hipStream_t s, const TopkDP& d, int metric, int tn, int wn, int qbu, dim3 grid, size_t lds, bool resident_only);
+// resident_only: MRAG_ENOTSUP instead of the two-launch form; depth = 16, or 32 for 17 <= k <= 32 (own instantiations where a second scoring follows: "l2")
+MRAG_FAMILY_LAUNCHER launch_topk_dense(hipStream_t s, const TopkDP& d, int metric, int tn, int wn, int qbu, int depth, dim3 grid, size_t lds, bool resident_only);

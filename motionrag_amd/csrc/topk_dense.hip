@@ -35,13 +35,17 @@ constexpr int DENSE_SCR = ((257 + 4 * DENSE_BUF) * 8 + (2 + 2048 + 2 + 2048) * 4
 // about `keep` runs of 128 bytes out of the query's 40 KB at 10 000 rows -- and ALL of them at once: the passing groups are listed first, then every thread
 // loads its elements of the list (one memory round trip; the first form walked the groups two at a time, a dependent load each: 18 us per query).  The
 // scores at or under the bound (about `keep` again) meet in one LDS array and are ordered by counting ranks.
+// DEPTH = 16, or 32 for the wide lists with a second scoring (keep = max(16, k) <= 32).  Nothing below is sized by `keep` beyond keep <= 64 (the bound is a
+// rank among the 64 lane minima; every merge carries 64 candidates): the compaction array holds CAP scores whatever `keep` is, more than CAP take the
+// per-wave path, whose buffer holds < 64 left over + <= 64 new entries per step.
+template <int DEPTH = 16>
 __device__ __forceinline__ void dense_select(const TopkDP& p, const int q, const bool store, const int lt, Cand* sh, Cand* bufs, int* ctr) {
   constexpr int CAP = 4 * DENSE_BUF;
   const int lane = lt & 63, wave = lt >> 6;
   const int ngrp = p.ld >> 5;
   const float* D = p.dist + (long long)q * p.ld;
   const float* G = p.gmin + (long long)q * ngrp;
-  const int keep = p.mp.rescore ? 16 : p.mp.k;
+  const int keep = topk_keep<DEPTH>(p.mp);
   int* glist = ctr + 2;
   float* gsh = (float*)(glist + 2048 + 2);              // [ngrp]: the query's group minima, loaded ONCE by the 256 threads (two loads in flight each)
   Cand inf; inf.d = INFINITY; inf.r = INT_MAX;
@@ -167,12 +171,12 @@ __device__ __forceinline__ void dense_select(const TopkDP& p, const int q, const
     if (wave == 0)
       for (int w = 1; w < 4; ++w) run = wave_merge_top(run, sh[w * 64 + lane], lane);
   }
-  finish_query(p.mp, q, run, sh, lt, store);
+  finish_query<DEPTH>(p.mp, q, run, sh, lt, store);
 }
 
 // QBU = queries a workgroup USES of the 32 TN WN its LDS image holds.  96 of 128 (the eight-wave workgroup whose second query group computes ONE of its two tiles):
 // three 32-query tiles per workgroup -- BASELINE config #1's 632 tiles then quantise to 3 per busy CU (237 workgroups) instead of 4 (158), with two waves per SIMD.
-template <int METRIC, int TN, int WN, int QBU = 32 * TN * WN>
+template <int METRIC, int TN, int WN, int QBU = 32 * TN * WN, int DEPTH = 16>
 __global__ __launch_bounds__(256 * WN, TN * WN == 1 ? 3 : WN == 1 ? 2 : 1) void topk_dense_kernel(const TopkDP p) {   // (waves per SIMD: 3 / 2 / 2 workgroups per CU)
   constexpr int WM = 4, NW = WM * WN, NT = 64 * NW, RB = 32 * WM, QB = 32 * TN * WN, NST = dense_stages(TN * WN);
   static_assert(QBU % 32 == 0 && QBU <= QB && QBU > QB - 32 * TN, "only the last query group may run short");
@@ -406,7 +410,7 @@ __global__ __launch_bounds__(256 * WN, TN * WN == 1 ? 3 : WN == 1 ? 2 : 1) void 
   if (mode == 1) {
     for (long long idx = ticket; idx * NG < p.nq; idx += p.total) {
       const int q = (int)idx * NG + (tid >> 8);
-      dense_select(p, q < p.nq ? q : p.nq - 1, q < p.nq, tid & 255, sh, bufs, glist);
+      dense_select<DEPTH>(p, q < p.nq ? q : p.nq - 1, q < p.nq, tid & 255, sh, bufs, glist);
     }
     return;
   }
@@ -417,16 +421,17 @@ __global__ __launch_bounds__(256 * WN, TN * WN == 1 ? 3 : WN == 1 ? 2 : 1) void 
     __syncthreads();
     if ((long long)claim * NG >= p.nq) break;
     const int q = (int)claim * NG + (tid >> 8);
-    dense_select(p, q < p.nq ? q : p.nq - 1, q < p.nq, tid & 255, sh, bufs, glist);
+    dense_select<DEPTH>(p, q < p.nq ? q : p.nq - 1, q < p.nq, tid & 255, sh, bufs, glist);
   }
 }
 
 // the finishing phase as a launch of its own (a workgroup per query): the dense form of tables whose grid is not resident at once
+template <int DEPTH>
 __global__ __launch_bounds__(256) void topk_dense_finish_kernel(const TopkDP p) {
   __shared__ __attribute__((aligned(16))) char scr[DENSE_SCR];
   Cand* sh = (Cand*)scr;
   Cand* bufs = sh + 257;
-  dense_select(p, blockIdx.x, true, threadIdx.x, sh, bufs, (int*)(bufs + 4 * DENSE_BUF));
+  dense_select<DEPTH>(p, blockIdx.x, true, threadIdx.x, sh, bufs, (int*)(bufs + 4 * DENSE_BUF));
 }
 
 // compute units of the current device (the grid wait of the one-launch form is taken only when the runtime's occupancy x this count holds the whole grid)
@@ -441,9 +446,9 @@ inline int dense_cus() {
 }
 
 // one instantiation: the occupancy query (once per instantiation and process), the launch and, without the grid wait, the finishing launch
-template <int M, int T, int W, int U>
+template <int M, int T, int W, int U, int DEPTH>
 int launch_dense(hipStream_t s, TopkDP d, dim3 grid, size_t lds, bool resident_only) {
-  auto kfn = topk_dense_kernel<M, T, W, U>;
+  auto kfn = topk_dense_kernel<M, T, W, U, DEPTH>;
   static int occ = -1;
   if (occ < 0) {
     hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -459,27 +464,30 @@ int launch_dense(hipStream_t s, TopkDP d, dim3 grid, size_t lds, bool resident_o
   MRAG_LAUNCH_CHECK();
   MRAG_COUNT(MRAG_K_TOPK_DENSE);
   if (d.total == 0) {
-    MRAG_LAUNCH(topk_dense_finish_kernel, dim3(d.nq), dim3(256), 0, s, d);
+    MRAG_LAUNCH(topk_dense_finish_kernel<DEPTH>, dim3(d.nq), dim3(256), 0, s, d);
     MRAG_LAUNCH_CHECK();
     MRAG_COUNT(MRAG_K_TOPK_DENSE_FINISH);
   }
   return MRAG_OK;
 }
 
-// the 8 instantiations: (tn, wn, queries used) = (1, 1, 32) (2, 1, 64) (2, 2, 128) (2, 2, 96), per metric
-template <int M>
+// the 8 instantiations of depth 16: (tn, wn, queries used) = (1, 1, 32) (2, 1, 64) (2, 2, 128) (2, 2, 96), per metric; depth 32: the same four for "l2" (its
+// second scoring is what the depth changes; "dot" selects `k` of up to 64 in the depth-16 code as it stands)
+template <int M, int DEPTH>
 int launch_dense_tile(hipStream_t s, const TopkDP& d, int tn, int wn, int qbu, dim3 grid, size_t lds, bool resident_only) {
   switch ((tn * 8 + wn) * 256 + qbu) {
-    case (1 * 8 + 1) * 256 + 32: return launch_dense<M, 1, 1, 32>(s, d, grid, lds, resident_only);
-    case (2 * 8 + 1) * 256 + 64: return launch_dense<M, 2, 1, 64>(s, d, grid, lds, resident_only);
-    case (2 * 8 + 2) * 256 + 128: return launch_dense<M, 2, 2, 128>(s, d, grid, lds, resident_only);
-    case (2 * 8 + 2) * 256 + 96: return launch_dense<M, 2, 2, 96>(s, d, grid, lds, resident_only);
+    case (1 * 8 + 1) * 256 + 32: return launch_dense<M, 1, 1, 32, DEPTH>(s, d, grid, lds, resident_only);
+    case (2 * 8 + 1) * 256 + 64: return launch_dense<M, 2, 1, 64, DEPTH>(s, d, grid, lds, resident_only);
+    case (2 * 8 + 2) * 256 + 128: return launch_dense<M, 2, 2, 128, DEPTH>(s, d, grid, lds, resident_only);
+    case (2 * 8 + 2) * 256 + 96: return launch_dense<M, 2, 2, 96, DEPTH>(s, d, grid, lds, resident_only);
     default: return MRAG_ENOTSUP;
   }
 }
 
 }  // namespace
 
-extern "C" int launch_topk_dense(hipStream_t s, const TopkDP& d, int metric, int tn, int wn, int qbu, dim3 grid, size_t lds, bool resident_only) {
-  return metric == 0 ? launch_dense_tile<0>(s, d, tn, wn, qbu, grid, lds, resident_only) : launch_dense_tile<1>(s, d, tn, wn, qbu, grid, lds, resident_only);
+extern "C" int launch_topk_dense(hipStream_t s, const TopkDP& d, int metric, int tn, int wn, int qbu, int depth, dim3 grid, size_t lds, bool resident_only) {
+  if (depth != 16 && depth != 32) return MRAG_ENOTSUP;
+  if (metric != 0) return launch_dense_tile<1, 16>(s, d, tn, wn, qbu, grid, lds, resident_only);
+  return depth == 32 ? launch_dense_tile<0, 32>(s, d, tn, wn, qbu, grid, lds, resident_only) : launch_dense_tile<0, 16>(s, d, tn, wn, qbu, grid, lds, resident_only);
 }

@@ -18,9 +18,12 @@ namespace {
 //     the LDS-DMA of slab i + NST - 1 is issued under the MFMAs of slab i behind a COUNTED vmcnt wait; the stream runs across the row blocks of a workgroup;
 //   * accumulator layout: lane (n = lane & 31, h = lane >> 5) holds query n of a 32-query tile against rows (reg & 3) + 8 (reg >> 2) + 4 h: after a row block a
 //     lane tests its 16 rows against ITS query's current k-th distance (a register).  Survivors are rare once the lists are warm; they go, one per lane and
-//     round, through per-query slots to the query's OWNER thread, which inserts them into the workgroup's sorted top-16 list in LDS and republishes the
+//     round, through per-query slots to the query's OWNER thread, which inserts them into the workgroup's sorted top-LIST list in LDS and republishes the
 //     threshold -- best candidates first, so the thresholds of a cold list converge in about k rounds;
-//   * per-workgroup lists [query][part][16] leave through the workspace and the merge kernel (LIST = 16) finishes, filter order included.
+//   * per-workgroup lists [query][part][LIST] leave through the workspace and the merge kernel (the same LIST) finishes, filter order included;
+//   * LIST = 16 (k <= 16) or 32 (the wide lists, 17 <= k <= 32: twice the owner's insertion chain and list registers; at most 128 queries per workgroup,
+//     since 256 lists of 33 + 9 entries beside the two-stage ring exceed the CU's 160 KB, and four waves, since the eight-wave tile's 256 registers per lane
+//     do not hold the 32-deep chain: it spilled to scratch inside the selection).
 
 // per call: the shared thresholds start at +inf; |q|^2 of every query in the fan-out kernel's order (chains over features
 // 8c + t and 8c + 4 + t, added once) when the metric needs it.  One wave per query: the row comes into LDS with coalesced 16-byte loads, then lane 0 runs the
@@ -48,10 +51,11 @@ __global__ __launch_bounds__(64) void topk_qq_kernel(const float* q, float* qq, 
 
 // WN = 2: eight waves -- four row groups x two query groups of TN tiles each -- so every SIMD holds TWO waves and one's LDS-read / DMA-issue / barrier
 // stalls pass under the other's MFMAs (the 256-query workgroup: TN = 4, WN = 2; as four waves of TN = 8 its matrix pipe idled a quarter of the stream)
-template <int METRIC, int TN, int WN>
+template <int METRIC, int TN, int WN, int LIST = 16>
 __global__ __launch_bounds__(256 * WN) void topk_mfma_kernel(const TopkMP p) {
+  static_assert(LIST == 16 || (LIST == 32 && TN <= 4 && WN == 1), "list depth: 16, or 32 on four-wave tiles of at most 128 queries");
   constexpr int WM = 4, NW = WM * WN, NT = 64 * NW, RB = 32 * WM, QB = 32 * TN * WN, NST = mfma_stages(TN * WN);
-  constexpr int STAGE = (RB + QB) * 128, NPIECE = (RB + QB) / 8, PPW = NPIECE / NW, NTAB = (RB / 8) / NW, LSTR = 17, NSLOT = 2 * WM;
+  constexpr int STAGE = (RB + QB) * 128, NPIECE = (RB + QB) / 8, PPW = NPIECE / NW, NTAB = (RB / 8) / NW, LSTR = LIST + 1, NSLOT = 2 * WM;   // (LSTR odd: the owners' list reads spread over the banks)
   static_assert(NPIECE % NW == 0 && (RB / 8) % NW == 0 && PPW == NTAB + TN, "every wave issues the same number of LDS-DMA pieces per slab (the counted vmcnt wait relies on it)");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   Cand* lists = (Cand*)(smem + NST * STAGE);        // [QB][LSTR]: sorted ascending, entries >= k stay +inf
@@ -257,11 +261,11 @@ __global__ __launch_bounds__(256 * WN) void topk_mfma_kernel(const TopkMP p) {
       if (!__syncthreads_or(any ? 1 : 0)) break;
       if (tid < QB) {                                 // the owner of query tid: at most NSLOT insertions into its sorted list
         // the list and the round's candidates come into REGISTERS in two bursts of independent LDS reads; every insertion is then a fixed chain of
-        // compare / select steps (the list keeps its best 16: entries k .. 15 are harmless extras, the threshold is entry k - 1).  A pointer-chasing
+        // compare / select steps (the list keeps its best LIST: entries k .. LIST - 1 are harmless extras, the threshold is entry k - 1).  A pointer-chasing
         // insertion in LDS cost ~20 k cycles per round -- two dependent LDS accesses per shifted entry -- and the rounds are workgroup-synchronous.
         Cand* Lp = lists + tid * LSTR;
-        float Ld[16], cd[NSLOT];
-        int Lr[16], cr[NSLOT];
+        float Ld[LIST], cd[NSLOT];
+        int Lr[LIST], cr[NSLOT];
         bool anyc = false;
 #pragma unroll
         for (int si = 0; si < NSLOT; ++si) {
@@ -271,7 +275,7 @@ __global__ __launch_bounds__(256 * WN) void topk_mfma_kernel(const TopkMP p) {
         }
         if (anyc) {
 #pragma unroll
-          for (int e = 0; e < 16; ++e) { const Cand l = Lp[e]; Ld[e] = l.d; Lr[e] = l.r; }
+          for (int e = 0; e < LIST; ++e) { const Cand l = Lp[e]; Ld[e] = l.d; Lr[e] = l.r; }
           auto less = [](float ad, int ar, float bd2, int br2) { return ad < bd2 || (ad == bd2 && ar < br2); };
           // one insertion per loop trip, best candidate first: the trip count is the LARGEST number of candidates any owner of the wave holds this round
           // (1-2 once the lists are warm), not NSLOT -- a wave pays every trip of its busiest lane with all 64 lanes
@@ -286,7 +290,7 @@ __global__ __launch_bounds__(256 * WN) void topk_mfma_kernel(const TopkMP p) {
             for (int si = 0; si < NSLOT; ++si)
               if (si == ms) { cd[si] = INFINITY; cr[si] = INT_MAX; }
 #pragma unroll
-            for (int e = 15; e >= 1; --e) {
+            for (int e = LIST - 1; e >= 1; --e) {
               const bool before_prev = less(md, mr, Ld[e - 1], Lr[e - 1]), before_this = less(md, mr, Ld[e], Lr[e]);
               Ld[e] = before_prev ? Ld[e - 1] : (before_this ? md : Ld[e]);
               Lr[e] = before_prev ? Lr[e - 1] : (before_this ? mr : Lr[e]);
@@ -298,7 +302,7 @@ __global__ __launch_bounds__(256 * WN) void topk_mfma_kernel(const TopkMP p) {
           float thd = Ld[0];
           int thr = Lr[0];
 #pragma unroll
-          for (int e = 0; e < 16; ++e) {
+          for (int e = 0; e < LIST; ++e) {
             Cand l; l.d = Ld[e]; l.r = Lr[e];
             Lp[e] = l;
             if (e == p.k - 1) { thd = Ld[e]; thr = Lr[e]; }
@@ -331,31 +335,38 @@ __global__ __launch_bounds__(256 * WN) void topk_mfma_kernel(const TopkMP p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ring's last NST - 1 (redundant) slabs must have landed before the workgroup gives its LDS back
   __syncthreads();
   if (tid < QB && q0 + tid < p.nq) {
-    Cand* out = p.lists + ((long long)(q0 + tid) * p.nparts + part) * 16;
+    Cand* out = p.lists + ((long long)(q0 + tid) * p.nparts + part) * LIST;
     const Cand* L = lists + tid * LSTR;
-    for (int e = 0; e < 16; ++e) out[e] = e < p.k ? L[e] : inf;
+    for (int e = 0; e < LIST; ++e) out[e] = e < p.k ? L[e] : inf;
   }
 }
 
 using MfmaKernel = void (*)(TopkMP);
 
-// the 10 instantiations: (tiles per query group, query groups) = (1, 1) (2, 1) (4, 1) (4, 2) (2, 2), per metric (256 queries per workgroup: eight waves of four tiles)
-template <int M>
+// the 10 instantiations of depth 16: (tiles per query group, query groups) = (1, 1) (2, 1) (4, 1) (4, 2) (2, 2), per metric (256 queries per workgroup: eight
+// waves of four tiles); the 6 of depth 32: (1, 1) (2, 1) (4, 1)
+template <int M, int LIST>
 MfmaKernel mfma_kernel(int tn, int wn) {
   switch (tn * 8 + wn) {
-    case 1 * 8 + 1: return topk_mfma_kernel<M, 1, 1>;
-    case 2 * 8 + 1: return topk_mfma_kernel<M, 2, 1>;
-    case 4 * 8 + 1: return topk_mfma_kernel<M, 4, 1>;
-    case 8 * 8 + 2: return topk_mfma_kernel<M, 4, 2>;
-    case 4 * 8 + 2: return topk_mfma_kernel<M, 2, 2>;
+    case 1 * 8 + 1: return topk_mfma_kernel<M, 1, 1, LIST>;
+    case 2 * 8 + 1: return topk_mfma_kernel<M, 2, 1, LIST>;
+    case 4 * 8 + 1: return topk_mfma_kernel<M, 4, 1, LIST>;
+    case 8 * 8 + 2:
+      if constexpr (LIST == 16) return topk_mfma_kernel<M, 4, 2, LIST>;
+      else return nullptr;
+    case 4 * 8 + 2:
+      if constexpr (LIST == 16) return topk_mfma_kernel<M, 2, 2, LIST>;
+      else return nullptr;
     default: return nullptr;
   }
 }
 
 }  // namespace
 
-extern "C" int launch_topk_mfma(hipStream_t s, const TopkMP& m, int metric, int tn, int wn, dim3 grid, size_t lds) {
-  const MfmaKernel kfn = metric == 0 ? mfma_kernel<0>(tn, wn) : mfma_kernel<1>(tn, wn);
+extern "C" int launch_topk_mfma(hipStream_t s, const TopkMP& m, int metric, int tn, int wn, int list, dim3 grid, size_t lds) {
+  if (list != 16 && list != 32) return MRAG_ENOTSUP;
+  const MfmaKernel kfn = list == 16 ? (metric == 0 ? mfma_kernel<0, 16>(tn, wn) : mfma_kernel<1, 16>(tn, wn))
+                                    : (metric == 0 ? mfma_kernel<0, 32>(tn, wn) : mfma_kernel<1, 32>(tn, wn));
   if (!kfn) return MRAG_ENOTSUP;
   MRAG_LAUNCH(topk_qq_kernel, dim3(m.nq), dim3(64), 0, s, m.q, const_cast<float*>(m.qq), m.tau_g, m.nq, m.dim, metric == 0 ? 1 : 0);
   MRAG_LAUNCH_CHECK();

@@ -258,8 +258,8 @@ extern "C" int launch_topk_scan(hipStream_t s, const TopkP& p, int qt, int jc, b
 }
 
 extern "C" int launch_topk_merge(hipStream_t s, const TopkP& p, int list) {
-  if (list != 64 && list != 16) return MRAG_ENOTSUP;
-  const TopkKernel kfn = list == 64 ? topk_merge_kernel<64> : topk_merge_kernel<16>;
+  if (list != 64 && list != 16 && list != 32) return MRAG_ENOTSUP;
+  const TopkKernel kfn = list == 64 ? topk_merge_kernel<64> : list == 32 ? topk_merge_kernel<32> : topk_merge_kernel<16>;
   MRAG_LAUNCH(kfn, dim3(p.nq), dim3(256), 0, s, p);
   return (int)hipGetLastError();
 }

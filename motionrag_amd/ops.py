@@ -804,15 +804,17 @@ def cfg_dpm_step_(v_pred: torch.Tensor, latents: torch.Tensor, x0_prev: torch.Te
 _TOPK_WS = {}
 
 
-def topk_workspace(device: torch.device, N: int, Q: int) -> torch.Tensor:
+def topk_workspace(device: torch.device, N: int, Q: int, k: int = 0) -> torch.Tensor:
     """scratch of mrag_topk_f32, one ZEROED buffer per (device, stream, N, Q): its first 64 bytes are the arrival counters of the
-    single-launch form, zero on first use and left zero by every call (include/mrag_hip.h)"""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream, N, Q)
+    single-launch form, zero on first use and left zero by every call (include/mrag_hip.h).  `k` > 16 (the wide lists of the fan-out form) sizes the
+    buffer by mrag_topk_workspace_bytes_k and keeps it under a key of its own, (.., N, Q, k): the buffers of every other call are the ones they were."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream, N, Q) + ((k,) if k > 16 else ())
     ws = _TOPK_WS.get(key)
     if ws is None:
         if len(_TOPK_WS) > 64:
             _TOPK_WS.clear()
-        ws = _TOPK_WS[key] = torch.zeros(_lib.lib().mrag_topk_workspace_bytes(N, Q), dtype=torch.uint8, device=device)
+        L = _lib.lib()
+        ws = _TOPK_WS[key] = torch.zeros(L.mrag_topk_workspace_bytes_k(N, Q, k) if k > 16 else L.mrag_topk_workspace_bytes(N, Q), dtype=torch.uint8, device=device)
     return ws
 
 
@@ -824,8 +826,9 @@ def topk(db: torch.Tensor, queries: torch.Tensor, k: int, *, metric: str = "l2",
     """flat-scan top-k: returns (rows int32 [Q, k], dist fp32 [Q, k]) sorted by (dist asc, row asc).  `out` = (rows, dist) buffers to fill
     (a caller that searches repeatedly keeps them: no allocation on the call path).  `postfilter`: rows of the excluded group are dropped
     AFTER the k nearest were selected (lancedb's `where(..., prefilter=False)`; possibly < k results, tail row -1) instead of before.
-    `order`: the distance's summation order (include/mrag_hip.h): "chain16" (the scan kernel), "mfma" (the fan-out kernel: >= 16 queries, k <= 16: one
-    pass over the table per 256 queries on fp32 MFMAs) or "auto" (mfma where it applies)."""
+    `order`: the distance's summation order (include/mrag_hip.h): "chain16" (the scan kernel), "mfma" (the fan-out kernel: >= 16 queries, k <= 32: one
+    pass over the table per 256 queries on fp32 MFMAs -- per 128 at 17 <= k <= 32, the wide lists) or "auto" (mfma where it applies with k <= 16: the wide
+    lists select other rows than the scan at the list's edge, so only a caller that names "mfma" / "mfma_stream" / "mfma_nowait" gets them)."""
     _dev(db, torch.float32, "db"); _dev(queries, torch.float32, "queries")
     if not db.is_contiguous() or not queries.is_contiguous():
         raise ValueError("topk: contiguous db / queries required")
@@ -834,7 +837,7 @@ def topk(db: torch.Tensor, queries: torch.Tensor, k: int, *, metric: str = "l2",
     m = {"l2": 0, "dot": 1}[metric]
     if exclude is not None:
         _dev(group, torch.int32, "group"); _dev(exclude, torch.int32, "exclude")
-    ws = topk_workspace(db.device, N, Q)
+    ws = topk_workspace(db.device, N, Q, k if TOPK_ORDER[order] >= 2 else 0)
     if Q <= 4:
         ws[:64].zero_()      # arrival counters of the single-launch form: re-zeroed on THIS call path (an aborted earlier launch cannot poison it); TopkPlan is the no-extra-launch path
     if out is None:
@@ -880,7 +883,8 @@ class TopkPlan:
     """A prepared search over a resident database: every buffer (query tile, exclusion ids, workspace, outputs) is allocated once and every
     ctypes argument is built once, so a query costs ONE C-ABI call -- for <= 4 queries one kernel launch (scan + merge fused) -- and nothing is
     allocated on the call path (the latency-bound interactive search of src/data/rag.py:63-80: 10 k rows stream in ~7 us, everything above
-    that was host overhead).  `graph=True` additionally records the launch in a HIP graph (`replay()`)."""
+    that was host overhead).  `graph=True` additionally records the launch in a HIP graph (`replay()`).  `order` as in `topk` (the fan-out orders at
+    17 <= k <= 32 size the private workspace by mrag_topk_workspace_bytes_k)."""
 
     def __init__(self, db: torch.Tensor, n_queries: int, k: int, *, metric: str = "l2", group: Optional[torch.Tensor] = None, graph: bool = False,
                  postfilter: bool = False, order: str = "auto"):
@@ -895,7 +899,8 @@ class TopkPlan:
         self.rows = torch.empty(n_queries, k, dtype=torch.int32, device=dev)
         self.dist = torch.empty(n_queries, k, dtype=torch.float32, device=dev)
         L = _lib.lib()
-        self._ws = torch.zeros(L.mrag_topk_workspace_bytes(N, n_queries), dtype=torch.uint8, device=dev)   # private: counters stay consistent
+        wide = TOPK_ORDER[order] >= 2 and k > 16
+        self._ws = torch.zeros(L.mrag_topk_workspace_bytes_k(N, n_queries, k) if wide else L.mrag_topk_workspace_bytes(N, n_queries), dtype=torch.uint8, device=dev)   # private: counters stay consistent
         self._fn = L.mrag_topk_f32
         self._args = (_p(db), _p(group) if group is not None else None, N, D, _p(self.queries), _p(self.exclude) if group is not None else None,
                       n_queries, k, {"l2": 0, "dot": 1}[metric], _p(self.rows), _p(self.dist), _p(self._ws), self._ws.numel(), int(bool(postfilter)),

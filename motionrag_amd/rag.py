@@ -174,11 +174,20 @@ def add_to_db(annotations: List[dict], embeddings: Optional[np.ndarray] = None, 
 class RAGDatabase:
     """src/data/rag.py:11-15; `metric` is LanceDB's: 'l2' (its default without an index; `_distance` is the squared
     L2 distance) or 'dot' (`_distance = 1 - dot`, the metric of the index build_rag_database.py:52 creates).  `image_metric`: the metric of searches
-    over the image column ('l2': the reference builds no index on `image_embedding`, and text_image_search's temporary table never has one)."""
+    over the image column ('l2': the reference builds no index on `image_embedding`, and text_image_search's temporary table never has one).
+
+    `wide_fanout` (default False; an attribute that may be set later): batch searches of 16 or more queries with 16 < top_k <= 32 -- text_search_batch,
+    image_search_batch and stage 1 of text_image_search_batch, e.g. the 21 rows `rag_text_image` asks for -- run the fan-out form (`ops.topk(order="mfma")`:
+    one pass over the table per 128 queries) instead of the scan form's pass per 16 queries.  What changes: WHICH rows make the list at its edge follows the
+    fan-out form's selection ("l2": the top_k nearest under the expanded score |q|^2 + |x|^2 - 2 q.x, scored again exactly and re-ranked; a row closer than
+    the expansion's error to the top_k-th may swap with it), as batches at top_k <= 16 already behave; the distance a row is given does not depend on the
+    form.  Single-query calls (and batches of fewer than 16) stay on the scan form.  Off by default because it moves results that were pinned before the
+    wide lists existed."""
 
     def __init__(self, db_path: str, table_name: str, device: str = "cuda", metric: str = "l2", embedder: Optional[Callable] = None,
-                 prefilter: bool = False, image_metric: str = "l2"):
+                 prefilter: bool = False, image_metric: str = "l2", wide_fanout: bool = False):
         self.prefilter = bool(prefilter)          # lancedb's `where(..., prefilter=)`; False = its 0.14.0 default (module docstring)
+        self.wide_fanout = bool(wide_fanout)
         tdir = os.path.join(db_path, table_name)
         self.vectors_host = np.load(os.path.join(tdir, "vectors.npy"), mmap_mode="c")      # a copy-on-write view of the file (never written): pages stream through on upload
         self._image_path = os.path.join(tdir, IMAGE_FILE)
@@ -198,10 +207,12 @@ class RAGDatabase:
 
     @classmethod
     def from_arrays(cls, vectors: np.ndarray, rows, device: str = "cuda", metric: str = "l2", embedder=None, prefilter: bool = False,
-                    image_vectors: Optional[np.ndarray] = None, image_metric: str = "l2") -> "RAGDatabase":
-        """`rows`: list of row dicts in the reference's schema, or an Arrow table with those columns; `image_vectors` [N, D_img]: the image column"""
+                    image_vectors: Optional[np.ndarray] = None, image_metric: str = "l2", wide_fanout: bool = False) -> "RAGDatabase":
+        """`rows`: list of row dicts in the reference's schema, or an Arrow table with those columns; `image_vectors` [N, D_img]: the image column;
+        `wide_fanout`: see the class docstring"""
         self = cls.__new__(cls)
         self.prefilter = bool(prefilter)
+        self.wide_fanout = bool(wide_fanout)
         self.vectors_host = vectors if (isinstance(vectors, np.ndarray) and vectors.dtype == np.float32) else np.ascontiguousarray(vectors, dtype=np.float32)
         self._image_path = IMAGE_FILE
         self.image_vectors_host = None if image_vectors is None else (
@@ -259,6 +270,10 @@ class RAGDatabase:
 
     def __len__(self):
         return self.meta.num_rows
+
+    def _batch_order(self, n_queries: int, top_k: int) -> str:
+        """`order` of a batch search's ops.topk: the fan-out form by name for the wide lists when `wide_fanout` is set, else the automatic choice"""
+        return "mfma" if (getattr(self, "wide_fanout", False) and n_queries >= 16 and 16 < top_k <= 32) else "auto"
 
     @property
     def rows(self) -> List[dict]:
@@ -362,7 +377,7 @@ class RAGDatabase:
             self._note_short(rows, top_k, post, exclude is not None)
             return [self._format(rows[i], dist[i], select, output_format) for i in range(Q)]
         else:
-            rows, dist = ops.topk(vectors, q, top_k, metric=metric, group=group, exclude=exclude, postfilter=post)
+            rows, dist = ops.topk(vectors, q, top_k, metric=metric, group=group, exclude=exclude, postfilter=post, order=self._batch_order(Q, top_k))
         rows, dist = rows.cpu().numpy(), dist.cpu().numpy()
         self._note_short(rows, top_k, post, exclude is not None)
         return [self._format(rows[i], dist[i], select, output_format) for i in range(Q)]
@@ -393,7 +408,7 @@ class RAGDatabase:
         if where is not None and any(w is not None for w in where):
             exclude = torch.tensor(self._exclude_ids(where), dtype=torch.int32, device=self.device)
             group = self.group
-        cand, _ = ops.topk(self.vectors, q, k0, metric=self.metric, group=group, exclude=exclude, postfilter=post)
+        cand, _ = ops.topk(self.vectors, q, k0, metric=self.metric, group=group, exclude=exclude, postfilter=post, order=self._batch_order(Q, k0))
         rows, _, dist = ops.topk_rerank(image_vectors, qi, cand, k1, metric=self.image_metric)
         both = torch.stack((rows, dist.view(torch.int32))).cpu().numpy()                        # ONE copy to the host
         rows, dist = both[0], both[1].view(np.float32)
