@@ -704,6 +704,22 @@ typedef struct mrag_groupnorm_args {
 } mrag_groupnorm_args;
 int64_t mrag_groupnorm_workspace_bytes(int64_t N, int64_t C, int32_t chunks);
 int mrag_groupnorm_bf16(void* stream, const mrag_groupnorm_args* args);
+/* The same GroupNorm split at the statistics, for a normalised extent that is sharded over W ranks (the (t, h, w) norms of the UNets' temporal layers
+ * under frame-parallel sharding, dist.FrameParallel): each rank holds x [N, HW, C] with HW its part of the extent.
+ *   partial:     `partial` [N, G, 2] fp32 <- (sum, sum of squares) per (n, group) of THIS shard: the statistics pass and the fold's fixed order (per channel
+ *                over the chunks, then per group over its channels).  Reads x, workspace, N, HW, C, G, chunks of the block; y may be NULL.
+ *   apply_stats: `partials` [W, N, G, 2] fp32 (the ranks' partials, gathered by the caller) are summed IN INDEX ORDER w = 0 .. W - 1 -- every rank that folds
+ *                the same list gets the same bits -- then mean, var = max(q / cnt - mean^2, 0), rsqrtf(var + eps) with cnt = HW_total * C / G (HW_total: the
+ *                rows of ALL shards per sample), and y = act(x * a_c + b_c) streams through the apply pass of the unsplit form.
+ * With W = 1, HW_total = HW and the same `chunks` the pair writes the bits of the unsplit call (the same arithmetic, an identity fold in the middle).
+ * emb, mod, fold and y_stride_n must be unset (MRAG_ENOTSUP: the temporal norms use none of them).  No allocation, nothing read back, plain launches on
+ * `stream`: 2 + 2 against the unsplit form's 3.  workspace: 16-byte aligned, the split size function's bytes; `partial` / `partials` 8-byte aligned. */
+int64_t mrag_groupnorm_split_workspace_bytes(int64_t N, int64_t C, int32_t chunks);
+int mrag_groupnorm_partial_bf16(void* stream, const mrag_groupnorm_args* args, float* partial);
+int mrag_groupnorm_apply_stats_bf16(void* stream, const mrag_groupnorm_args* args, const float* partials, int32_t W, int64_t HW_total);
+/* dst [B, A, R] <- src [A, B, R] bf16 (dst[b, a, :] = src[a, b, :]), R % 8 == 0, both 16-byte aligned, not in place: the packing copies either side of the
+ * frame <-> pixel all-to-all.  Bit-equal to a permute copy.  A, B <= 65535 and A * B * ceil(R / 8192) < 2^31, else MRAG_ENOTSUP.                       */
+int mrag_swap_outer_bf16(void* stream, const void* src, void* dst, int64_t A, int64_t B, int64_t R);
 /* row gather in front of the implicit-GEMM 3x3 convolution (pad 1, stride 1|2,
  * optional nearest x2 upsample of the source: openaimodel3d.py:52-107):
  * dst[(n,yo,xo), (ky,kx,c)] -> [N*Ho*Wo, Kpad], columns >= 9C zero.            */

@@ -38,12 +38,13 @@ SYMBOLS = [
     "mrag_resampler_workspace_bytes", "mrag_resampler_fwd", "mrag_cama_encoder_workspace_bytes", "mrag_cama_encoder_fwd",
     "mrag_quant_rows_e4m3", "mrag_gemm_fp8", "mrag_fp8_launch_counts", "mrag_conv_fp8", "mrag_conv_fp8_launch_counts",
     "mrag_layernorm_e4m3", "mrag_gemm_fp8_k64", "mrag_gemm_fp8_k64_launch_counts",
+    "mrag_groupnorm_split_workspace_bytes", "mrag_groupnorm_partial_bf16", "mrag_groupnorm_apply_stats_bf16", "mrag_swap_outer_bf16",
 ]
 
 
 # entry points whose result is not the int32 status code (their restype is set explicitly in lib())
 _NON_INT_RESULT = ("mrag_target_arch", "mrag_source_hash", "mrag_dispatch_name", "mrag_probe_mfma_flops", "mrag_probe_mfma_f32_flops", "mrag_gemm_workspace_bytes", "mrag_attn_workspace_bytes", "mrag_attn_fp8_workspace_bytes", "mrag_attn_joint_fp8_workspace_bytes", "mrag_topk_workspace_bytes", "mrag_topk_workspace_bytes_k", "mrag_groupnorm_workspace_bytes",
-                   "mrag_ddim_v_rescale_workspace_bytes", "mrag_resampler_workspace_bytes", "mrag_cama_encoder_workspace_bytes")
+                   "mrag_ddim_v_rescale_workspace_bytes", "mrag_resampler_workspace_bytes", "mrag_cama_encoder_workspace_bytes", "mrag_groupnorm_split_workspace_bytes")
 
 
 class HipLibraryMissing(RuntimeError):
@@ -346,6 +347,11 @@ def lib() -> ctypes.CDLL:
     L.mrag_groupnorm_workspace_bytes.argtypes = [c_int64, c_int64, c_int32]
     L.mrag_groupnorm_workspace_bytes.restype = c_int64
     L.mrag_groupnorm_bf16.argtypes = [c_void_p, POINTER(GroupNormArgs)]
+    L.mrag_groupnorm_split_workspace_bytes.argtypes = [c_int64, c_int64, c_int32]
+    L.mrag_groupnorm_split_workspace_bytes.restype = c_int64
+    L.mrag_groupnorm_partial_bf16.argtypes = [c_void_p, POINTER(GroupNormArgs), c_void_p]
+    L.mrag_groupnorm_apply_stats_bf16.argtypes = [c_void_p, POINTER(GroupNormArgs), c_void_p, c_int32, c_int64]
+    L.mrag_swap_outer_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64]
     L.mrag_im2col3x3_bf16.argtypes = [c_void_p, c_void_p, c_void_p] + [c_int32] * 7
     L.mrag_unfold_t3_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32]
     L.mrag_geglu_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64]

@@ -5,6 +5,9 @@
 //   mrag_groupnorm_bf16   nn.GroupNorm(32, C) [+ per-(n, c) embedding pre-add] [+ SiLU]
 //                         (lvdm/basics.py:81-88 GroupNorm32; openaimodel3d.py:152-181 ResBlock in/out layers, :258-268
 //                          TemporalConvBlock; attention.py:286,357 transformer norms)
+//   mrag_groupnorm_partial_bf16 / mrag_groupnorm_apply_stats_bf16   the same GroupNorm split at the statistics: one shard's (sum, sum of squares) out, every
+//                         shard's in (the (t, h, w) norms of the temporal layers when the frames / pixels are sharded over ranks)
+//   mrag_swap_outer_bf16  [A, B, R] -> [B, A, R] copy (the packing steps of the frame <-> pixel all-to-all)
 //   mrag_im2col3x3_bf16   row gather for nn.Conv2d 3x3 (stride 1 / 2, pad 1; optional nearest x2 upsample in front:
 //                         openaimodel3d.py:52-107 Downsample / Upsample, :152-181 ResBlock convs) -> implicit GEMM
 //   mrag_unfold_t3_bf16   row gather for nn.Conv3d (3,1,1), pad (1,0,0) (openaimodel3d.py:256-268)
@@ -163,12 +166,10 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GnP p) {
   }
 }
 
-// pass 2 (tiny): one workgroup per (group, n) folds the chunk partials of its channels in a FIXED order (bit-reproducible),
-// adds the analytic contribution of the per-(n, c) embedding, and writes per-channel scale / shift a_c, b_c to the workspace.
-__global__ __launch_bounds__(256) void gn_fold_kernel(const GnP p, float* ab) {
-  __shared__ float red_s[256], red_q[256];
-  __shared__ float ch_s[256], ch_q[256];
-  const int g = blockIdx.x, n = blockIdx.y, t = threadIdx.x;
+// the fold's fixed order (bit-reproducible), shared by the unsplit fold and the split form's partial: per channel over the chunks (k-slices, then the slices in order),
+// the analytic contribution of the per-(n, c) embedding, then per group over its channels.  The group's (sum, sum of squares) end up in red_s[0] / red_q[0].
+__device__ __forceinline__ void gn_group_sums(const GnP& p, const int g, const int n, float* red_s, float* red_q, float* ch_s, float* ch_q) {
+  const int t = threadIdx.x;
   const int cpg = (int)(p.C / p.G);          // <= 256 (host check)
   const int ksl = 256 / cpg;                 // k-slices: thread t sums channel (t % cpg) over chunks k = t / cpg, + ksl, ...
   const int cl = t % cpg, ks = t / cpg;
@@ -199,6 +200,15 @@ __global__ __launch_bounds__(256) void gn_fold_kernel(const GnP p, float* ab) {
     red_s[0] = s; red_q[0] = q;
   }
   __syncthreads();
+}
+
+// pass 2 (tiny): one workgroup per (group, n) folds the chunk partials of its channels (gn_group_sums) and writes per-channel scale / shift a_c, b_c to the workspace.
+__global__ __launch_bounds__(256) void gn_fold_kernel(const GnP p, float* ab) {
+  __shared__ float red_s[256], red_q[256];
+  __shared__ float ch_s[256], ch_q[256];
+  const int g = blockIdx.x, n = blockIdx.y, t = threadIdx.x;
+  const int cpg = (int)(p.C / p.G);
+  gn_group_sums(p, g, n, red_s, red_q, ch_s, ch_q);
   const float cnt = (float)p.HW * (float)cpg;
   const float mean = red_s[0] / cnt;
   const float var = fmaxf(red_q[0] / cnt - mean * mean, 0.f);
@@ -209,6 +219,41 @@ __global__ __launch_bounds__(256) void gn_fold_kernel(const GnP p, float* ab) {
     const float e = p.emb ? bf2f(p.emb[(long long)n * p.emb_stride + c]) : 0.f;
     ab[((long long)n * p.C + c) * 2] = ga * rstd;
     ab[((long long)n * p.C + c) * 2 + 1] = be + (e - mean) * ga * rstd;
+  }
+}
+
+// ---- GroupNorm with statistics from elsewhere (frame-parallel UNet: a rank holds one shard of the (t, h, w) extent of a temporal norm)
+// pass 2a: the fold's group sums (gn_group_sums: the same fixed order; emb is never set here) written to the caller's [N, G, 2] instead of being turned into
+// scale / shift.
+__global__ __launch_bounds__(256) void gn_partial_fold_kernel(const GnP p, float* partial) {
+  __shared__ float red_s[256], red_q[256];
+  __shared__ float ch_s[256], ch_q[256];
+  const int g = blockIdx.x, n = blockIdx.y;
+  gn_group_sums(p, g, n, red_s, red_q, ch_s, ch_q);
+  if (threadIdx.x == 0) {
+    partial[((long long)n * p.G + g) * 2] = red_s[0];
+    partial[((long long)n * p.G + g) * 2 + 1] = red_q[0];
+  }
+}
+
+// pass 2b: fold the W shards' [N, G, 2] entries IN INDEX ORDER (every rank folds the same list the same way: identical statistics without a broadcast; one entry is
+// taken as it is), then mean / rstd / scale / shift exactly as gn_fold_kernel forms them, with the count of ALL shards.  Every thread folds the (few) entries itself.
+__global__ __launch_bounds__(256) void gn_shards_fold_kernel(const GnP p, const float* partials, int W, long long hw_total, float* ab) {
+  const int g = blockIdx.x, n = blockIdx.y, t = threadIdx.x;
+  const int cpg = (int)(p.C / p.G);
+  const float* e = partials + ((long long)n * p.G + g) * 2;
+  const long long wstride = p.N * p.G * 2;
+  float s = e[0], q = e[1];
+  for (int w = 1; w < W; ++w) { s += e[w * wstride]; q += e[w * wstride + 1]; }
+  const float cnt = (float)hw_total * (float)cpg;
+  const float mean = s / cnt;
+  const float var = fmaxf(q / cnt - mean * mean, 0.f);
+  const float rstd = rsqrtf(var + p.eps);
+  if (t < cpg) {
+    const int c = g * cpg + t;
+    const float ga = p.gamma ? bf2f(p.gamma[c]) : 1.f, be = p.beta ? bf2f(p.beta[c]) : 0.f;
+    ab[((long long)n * p.C + c) * 2] = ga * rstd;
+    ab[((long long)n * p.C + c) * 2 + 1] = be + (0.f - mean) * ga * rstd;
   }
 }
 
@@ -299,6 +344,30 @@ __global__ __launch_bounds__(256) void gn_apply_mod_kernel(const GnP p, const fl
       v[e] = p.silu ? silu_f(o) : o;
     }
     *(u32x4*)(yb + (long long)px * p.C + c0) = pack8(v);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- outer-axis swap copy
+// dst[b, a, :] = src[a, b, :] for [A, B, R] -> [B, A, R], rows of Rv 16-byte vectors: the packing steps either side of the frame <-> pixel all-to-all of the
+// frame-parallel UNet (dist.FrameParallel).  The form of the library's stream copy (probe.hip): a workgroup moves one CONTIGUOUS run of 4 x 256 vectors (16 KiB, the
+// same run on both sides since a run never leaves its row), four nontemporal loads in flight per thread before the first store.  An item is (destination row, run of
+// that row); the last run of a row is guarded per vector, so a row of any length -- one vector included -- takes the same path.
+__global__ __launch_bounds__(256) void swap_outer_kernel(const u32x4* __restrict__ src, u32x4* __restrict__ dst, unsigned A, unsigned B, long long Rv, unsigned runs_per_row,
+                                                         unsigned items) {
+  constexpr int U = 4;
+  for (unsigned item = blockIdx.x; item < items; item += gridDim.x) {
+    const unsigned drow = item / runs_per_row, run = item - drow * runs_per_row;     // drow = b * A + a
+    const unsigned b = drow / A, a = drow - b * A;
+    const long long v0 = (long long)run * (256 * U) + threadIdx.x;
+    const u32x4* s = src + ((long long)a * B + b) * Rv;
+    u32x4* d = dst + (long long)drow * Rv;
+    u32x4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (v0 + u * 256 < Rv) v[u] = __builtin_nontemporal_load(s + v0 + u * 256);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (v0 + u * 256 < Rv) __builtin_nontemporal_store(v[u], d + v0 + u * 256);
   }
 }
 
@@ -554,6 +623,78 @@ extern "C" int mrag_groupnorm_bf16(void* stream, const mrag_groupnorm_args* a) {
   MRAG_LAUNCH(gn_apply_kernel, dim3((unsigned)bx, (unsigned)a->N), dim3(256), lds, s, p, (const float*)ab);
   MRAG_LAUNCH_CHECK();
   MRAG_COUNT(MRAG_K_GN_APPLY);
+  return MRAG_OK;
+}
+
+// ---- the split pair: statistics of one shard out, statistics of all shards in (include/mrag_hip.h)
+namespace {
+// what both halves check; `need_y`: the apply half
+inline int gn_split_check(const mrag_groupnorm_args* a, bool need_y) {
+  if (!a || !a->x || !a->workspace || (need_y && !a->y)) return MRAG_EINVAL;
+  if (a->N <= 0 || a->HW <= 0 || a->C <= 0 || a->G <= 0 || a->chunks <= 0) return MRAG_EINVAL;
+  if (a->C % 8 != 0 || a->C % a->G != 0) return MRAG_EINVAL;
+  if (a->emb || a->mod || a->fold || a->y_stride_n != 0) return MRAG_ENOTSUP;      // the temporal norms use none of them
+  if (a->C > 8192 || a->N > 65535 || a->chunks > 1024 || a->C / a->G > 256) return MRAG_ENOTSUP;
+  if (((uintptr_t)a->x | (uintptr_t)a->y | (uintptr_t)a->workspace) & 15) return MRAG_EINVAL;
+  return MRAG_OK;
+}
+}  // namespace
+
+extern "C" int64_t mrag_groupnorm_split_workspace_bytes(int64_t N, int64_t C, int32_t chunks) {
+  return mrag_groupnorm_workspace_bytes(N, C, chunks);                               // the same layout (the counters in front stay untouched)
+}
+
+extern "C" int mrag_groupnorm_partial_bf16(void* stream, const mrag_groupnorm_args* a, float* partial) {
+  const int rc = gn_split_check(a, false);
+  if (rc != MRAG_OK) return rc;
+  if (!partial || ((uintptr_t)partial & 7)) return MRAG_EINVAL;
+  GnP p{};
+  p.x = (const bf16_t*)a->x; p.part = (float*)((char*)a->workspace + GN_TICKET_BYTES);
+  p.N = a->N; p.HW = a->HW; p.C = a->C; p.G = a->G; p.chunks = a->chunks;
+  hipStream_t s = (hipStream_t)stream;
+  MRAG_LAUNCH(gn_stats_kernel<false>, dim3(a->chunks, (unsigned)a->N, (unsigned)((a->C + 2047) / 2048)), dim3(256), 0, s, p);
+  MRAG_LAUNCH_CHECK();
+  MRAG_COUNT(MRAG_K_GN_STATS);
+  MRAG_LAUNCH(gn_partial_fold_kernel, dim3((unsigned)a->G, (unsigned)a->N), dim3(256), 0, s, p, partial);
+  MRAG_LAUNCH_CHECK();
+  MRAG_COUNT(MRAG_K_GN_FOLD);
+  return MRAG_OK;
+}
+
+extern "C" int mrag_groupnorm_apply_stats_bf16(void* stream, const mrag_groupnorm_args* a, const float* partials, int32_t W, int64_t HW_total) {
+  const int rc = gn_split_check(a, true);
+  if (rc != MRAG_OK) return rc;
+  if (!partials || ((uintptr_t)partials & 7) || W < 1 || HW_total < a->HW) return MRAG_EINVAL;
+  GnP p{};
+  p.x = (const bf16_t*)a->x; p.y = (bf16_t*)a->y; p.gamma = (const bf16_t*)a->gamma; p.beta = (const bf16_t*)a->beta;
+  p.part = (float*)((char*)a->workspace + GN_TICKET_BYTES);
+  p.N = a->N; p.HW = a->HW; p.C = a->C; p.G = a->G; p.chunks = a->chunks; p.silu = a->silu; p.eps = a->eps;
+  float* ab = p.part + a->N * a->chunks * a->C * 2;                                  // where mrag_groupnorm_bf16 keeps them
+  p.ab = ab;
+  hipStream_t s = (hipStream_t)stream;
+  MRAG_LAUNCH(gn_shards_fold_kernel, dim3((unsigned)a->G, (unsigned)a->N), dim3(256), 0, s, p, partials, (int)W, (long long)HW_total, ab);
+  MRAG_LAUNCH_CHECK();
+  MRAG_COUNT(MRAG_K_GN_FOLD);
+  long long bx = (a->HW * (a->C / 8) + 1023) / 1024;          // the grid of mrag_groupnorm_bf16's apply pass
+  const long long cap = 4096 / a->N > 16 ? 4096 / a->N : 16;
+  if (bx > cap) bx = cap;
+  if (bx < 1) bx = 1;
+  MRAG_LAUNCH(gn_apply_kernel, dim3((unsigned)bx, (unsigned)a->N), dim3(256), (size_t)a->C * 2 * sizeof(float), s, p, (const float*)ab);
+  MRAG_LAUNCH_CHECK();
+  MRAG_COUNT(MRAG_K_GN_APPLY);
+  return MRAG_OK;
+}
+
+extern "C" int mrag_swap_outer_bf16(void* stream, const void* src, void* dst, int64_t A, int64_t B, int64_t R) {
+  if (!src || !dst || src == dst || A <= 0 || B <= 0 || R <= 0 || R % 8 != 0) return MRAG_EINVAL;
+  if (((uintptr_t)src | (uintptr_t)dst) & 15) return MRAG_EINVAL;
+  const long long Rv = R / 8, runs = (Rv + 1023) / 1024;
+  if (A > 65535 || B > 65535 || A * B * runs >= (1LL << 31)) return MRAG_ENOTSUP;   // 32-bit item arithmetic in the kernel
+  const long long items = A * B * runs;
+  const long long wgs = items < 256LL * 16 ? items : 256LL * 16;                     // the stream copy's 16 workgroups per CU
+  MRAG_LAUNCH(swap_outer_kernel, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, (const u32x4*)src, (u32x4*)dst, (unsigned)A, (unsigned)B, Rv, (unsigned)runs,
+              (unsigned)items);
+  MRAG_LAUNCH_CHECK();
   return MRAG_OK;
 }
 

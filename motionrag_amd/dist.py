@@ -284,3 +284,108 @@ def pixels_to_frames(y: torch.Tensor, world: int, group=None) -> torch.Tensor:
     recv = torch.empty_like(send)
     dist.all_to_all_single(recv, send, group=group)                                          # recv[r] = MY frames of rank r's pixel slab
     return recv.permute(1, 2, 0, 3, 4).reshape(b, t // world, world * hwl, c)
+
+
+class FrameParallel:
+    """Tier 2 for the UNet backbones (SURVEY 8e): ONE clip's frames sharded over the ranks of a node.  Spatial layers run on a rank's `t / world` frames;
+    every temporal layer (TemporalTransformer, TemporalConvBlock) runs on ALL frames of the rank's `hw / world` pixel slab, between `to_pixels` and
+    `to_frames`; a (t, h, w) GroupNorm takes its statistics from every rank through `gather_stats`.  Multi-GPU step time: unmeasured on hardware.
+
+    Transport: GPU tensors on an NCCL group exchange on the device (`all_to_all_single` / `all_gather_into_tensor`) with the library's swap copy
+    (`ops.swap_outer`) packing either side; GPU tensors on a gloo group (developer / test runs of several ranks on one GPU) are packed by the same
+    kernel and staged through the host, as `CFGParallel.gather_branches` does; CPU tensors take the torch path of `frames_to_pixels`.
+    `world == 1`: every method returns its argument and launches nothing."""
+
+    def __init__(self, rank: int, world: int, group=None):
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError(f"rank {rank} of world {world}")
+        self.rank, self.world, self.group = rank, world, group
+
+    # ---- geometry
+    def frames(self, t: int) -> range:
+        """this rank's frames of a clip of t"""
+        if t % self.world:
+            raise ValueError(f"{t} frames do not split evenly over {self.world} ranks")
+        tl = t // self.world
+        return range(self.rank * tl, (self.rank + 1) * tl)
+
+    def check(self, t: int, hws) -> None:
+        """ValueError unless t and every level's pixel count split over the ranks"""
+        self.frames(t)
+        for hw in hws:
+            if hw % self.world:
+                raise ValueError(f"a level of {hw} pixels does not split evenly over {self.world} ranks")
+
+    # ---- transport
+    def _host(self, x: torch.Tensor) -> bool:
+        return x.is_cuda and dist.get_backend(self.group) == "gloo"
+
+    def _a2a(self, send: torch.Tensor) -> torch.Tensor:
+        if self._host(send):
+            h = send.cpu()
+            r = torch.empty_like(h)
+            dist.all_to_all_single(r, h, group=self.group)
+            return r.to(send.device)
+        recv = torch.empty_like(send)
+        dist.all_to_all_single(recv, send, group=self.group)
+        return recv
+
+    def _swap(self, x: torch.Tensor, A: int, B: int, R: int) -> torch.Tensor:
+        """[A, B, R] -> [B, A, R] contiguous, whatever x's own shape (x contiguous)"""
+        if x.is_cuda:
+            from . import ops
+            return ops.swap_outer(x.view(A, B, R))
+        return x.view(A, B, R).permute(1, 0, 2).contiguous()
+
+    def to_pixels(self, x: torch.Tensor) -> torch.Tensor:
+        """x [b, t_loc, hw, c] (this rank's frames, all pixels) -> [b, t, hw / world, c] (all frames in frame order, this rank's pixel slab)"""
+        b, tl, hw, c = x.shape
+        W = self.world
+        if hw % W:
+            raise ValueError(f"{hw} pixels do not split over {W} ranks")
+        if W == 1:
+            return x
+        hwl = hw // W
+        send = self._swap(x.contiguous(), b * tl, W, hwl * c)                 # [peer, (b, t_loc), hw_loc * c]
+        recv = self._a2a(send)                                                # recv[r] = rank r's frames of MY pixel slab
+        return self._swap(recv, W, b, tl * hwl * c).view(b, W * tl, hwl, c)   # frame index = r * t_loc + i (rank-major == frame order)
+
+    def to_frames(self, y: torch.Tensor) -> torch.Tensor:
+        """inverse of `to_pixels`: y [b, t, hw_loc, c] -> [b, t / world, hw_loc * world, c]"""
+        b, t, hwl, c = y.shape
+        W = self.world
+        if t % W:
+            raise ValueError(f"{t} frames do not split over {W} ranks")
+        if W == 1:
+            return y
+        tl = t // W
+        send = self._swap(y.contiguous(), b, W, tl * hwl * c)                 # [peer, b, t_loc * hw_loc * c]
+        recv = self._a2a(send)                                                # recv[r] = MY frames of rank r's pixel slab
+        return self._swap(recv, W, b * tl, hwl * c).view(b, tl, W * hwl, c)
+
+    def _gather0(self, x: torch.Tensor) -> torch.Tensor:
+        """[...] per rank -> [world, ...] in rank order on every rank"""
+        x = x.contiguous()
+        if self._host(x) or not x.is_cuda:
+            h = x.cpu()
+            parts = [torch.empty_like(h) for _ in range(self.world)]
+            dist.all_gather(parts, h, group=self.group)
+            return torch.stack(parts).to(x.device)
+        out = torch.empty((self.world,) + tuple(x.shape), dtype=x.dtype, device=x.device)
+        dist.all_gather_into_tensor(out, x, group=self.group)
+        return out
+
+    def gather_stats(self, partial: torch.Tensor) -> torch.Tensor:
+        """this rank's GroupNorm partial [N, G, 2] fp32 -> [world, N, G, 2] in rank order on every rank: every rank folds the same list in the same order, so
+        the statistics are bit-identical everywhere without a broadcast"""
+        if self.world == 1:
+            return partial
+        return self._gather0(partial)
+
+    def gather_frames(self, y_local: torch.Tensor) -> torch.Tensor:
+        """end of the forward: y_local [b, t_loc, ...] -> [b, t, ...] on every rank (frame order)"""
+        if self.world == 1:
+            return y_local
+        g = self._gather0(y_local)                                            # [world, b, t_loc, ...]
+        b, tl = y_local.shape[:2]
+        return g.transpose(0, 1).reshape((b, self.world * tl) + tuple(y_local.shape[2:]))

@@ -59,6 +59,31 @@ def temb_proj(silu_emb, lin: nn.Linear) -> torch.Tensor:
     return silu_emb.proj(lin) if isinstance(silu_emb, TembBank) else ops.linear(silu_emb, lin.weight, lin.bias)
 
 
+# ------------------------------------------------------------------------------------------------------ frame-parallel sharding (tier 2)
+def set_frame_parallel(unet: nn.Module, fp) -> nn.Module:
+    """`fp`: a `dist.FrameParallel`, or None for the unsharded path (the default: same launches, same bits as a model that never saw this call).
+    With one set, `UNetModel.forward` still takes and returns the full `[b, c, t, h, w]` on every rank (the sampler stays replicated) but computes only
+    this rank's frames: spatial layers on `t / world` frames, temporal layers on all frames of `hw / world` pixels between two all-to-all transposes,
+    their (t, h, w) GroupNorms on statistics gathered from every rank.  A `FrameParallel` of world 1 is the unsharded path.  The launcher's one call
+    (INTEGRATION.md); multi-GPU step time is unmeasured on hardware."""
+    for m in unet.modules():
+        if isinstance(m, (UNetModel, TemporalTransformer, TemporalConvBlock)):
+            m.frame_parallel = fp
+    return unet
+
+
+def _sharding(m: nn.Module):
+    fp = m.frame_parallel
+    return fp if fp is not None and fp.world > 1 else None
+
+
+def _groupnorm_all_ranks(fp, x: torch.Tensor, gn: nn.GroupNorm, rows_total: int, silu: bool = False) -> torch.Tensor:
+    """GroupNorm of x [b, rows_loc, C] -- this rank's part of `rows_total` (t, h, w) rows per sample: partial sums of the shard, all-gather of the
+    [b, 32, 2] partials, then every rank folds them in rank order and normalises its shard (ops.groupnorm_partial / groupnorm_apply_stats)"""
+    partials = fp.gather_stats(ops.groupnorm_partial(x, 32))
+    return ops.groupnorm_apply_stats(x, partials, rows_total, gn.weight, gn.bias, 32, gn.eps, silu=silu)
+
+
 # ------------------------------------------------------------------------------------------------------ attention
 def set_attention_precision(module: nn.Module, precision: str = "bf16") -> nn.Module:
     """'bf16' (the reference's precision) or 'fp8': spatial self-attention (attention.py:189 with context None) of every CrossAttention under
@@ -236,7 +261,14 @@ class SpatialTransformer(nn.Module):
 
 
 class TemporalTransformer(nn.Module):
-    """attention.py:335-445 (only_self_att, no causal mask, no relative position)"""
+    """attention.py:335-445 (only_self_att, no causal mask, no relative position).
+
+    Frame-parallel (`set_frame_parallel`): the input is transposed FIRST (frames -> pixels), and everything else -- the GroupNorm, proj_in, the blocks,
+    proj_out and its residual -- runs on the pixel side, on all t frames of this rank's hw / world pixels; one transpose back at the end.  Both
+    transposes then move in_channels per row (proj_in widens the init block's 320 to 512), and the residual needs no exchange of its own.  The GroupNorm
+    statistics are therefore taken on the PIXEL side of the transpose: a rank's partial sums cover (all t, its pixel slab), not (its frames, all
+    pixels), which fixes the partition of the fp32 sums and with it the bits."""
+    frame_parallel = None
 
     def __init__(self, in_channels, n_heads, d_head, depth=1, dropout=0.0, context_dim=None, use_checkpoint=True, use_linear=False,
                  only_self_att=True, causal_attention=False, causal_block_size=1, relative_position=False, temporal_length=None,
@@ -255,6 +287,16 @@ class TemporalTransformer(nn.Module):
         """x [(b t), H, W, C]; GroupNorm statistics over (t, h, w) per sample (5-D input in the reference, :397-398)"""
         N, H, W, C = x.shape
         t, hw = N // b, H * W
+        fp = _sharding(self)
+        if fp is not None:
+            xp = fp.to_pixels(x.view(b, t, hw, C))                                                   # [b, t_all, hw_loc, C]
+            ta, hwl = xp.shape[1], xp.shape[2]
+            y = _groupnorm_all_ranks(fp, xp.view(b, ta * hwl, C), self.norm, ta * hw).view(b * ta, hwl, C)
+            y = ops.linear(y, lin_w(self.proj_in), self.proj_in.bias)
+            for blk in self.transformer_blocks:
+                y = blk(y, context=None, temporal=(b, ta, hwl))
+            y = ops.linear(y, lin_w(self.proj_out), self.proj_out.bias, epilogue=ops.EPI_RESID, resid=xp.view(b * ta, hwl, C))
+            return fp.to_frames(y.view(b, ta, hwl, C)).view(N, H, W, C)
         y = ops.groupnorm(x.view(b, t * hw, C), self.norm.weight, self.norm.bias, 32, self.norm.eps).view(N, hw, C)
         y = ops.linear(y, lin_w(self.proj_in), self.proj_in.bias)
         for blk in self.transformer_blocks:
@@ -264,7 +306,9 @@ class TemporalTransformer(nn.Module):
 
 # ------------------------------------------------------------------------------------------------------ conv blocks
 class TemporalConvBlock(nn.Module):
-    """openaimodel3d.py:240-281"""
+    """openaimodel3d.py:240-281.  Frame-parallel (`set_frame_parallel`): the block's input (also its residual) goes frames -> pixels, the four
+    GroupNorm -> (3,1,1) convolution stages run on all frames of this rank's pixel slab with statistics from every rank, and the result goes back."""
+    frame_parallel = None
 
     def __init__(self, in_channels, out_channels=None, dropout=0.0, spatial_aware=False):
         super().__init__()
@@ -280,6 +324,16 @@ class TemporalConvBlock(nn.Module):
         """x [(b t), HW, C]"""
         N, HW, C = x.shape
         t = N // b
+        fp = _sharding(self)
+        if fp is not None:
+            xp = fp.to_pixels(x.view(b, t, HW, C))                                                   # [b, t_all, hw_loc, C]
+            ta, hwl = xp.shape[1], xp.shape[2]
+            xp = xp.view(b * ta, hwl, C)
+            y = xp
+            for i, seq in enumerate((self.conv1, self.conv2, self.conv3, self.conv4)):
+                y = _groupnorm_all_ranks(fp, y.view(b, ta * hwl, y.shape[-1]), seq[0], ta * HW, silu=True).view(b * ta, hwl, -1)
+                y = conv_t3(y, seq[-1], b, ta, resid=xp if i == 3 else None)
+            return fp.to_frames(y.view(b, ta, hwl, C)).view(N, HW, C)
         y = x
         for i, seq in enumerate((self.conv1, self.conv2, self.conv3, self.conv4)):
             gn = seq[0]
@@ -371,6 +425,7 @@ class TimestepEmbedSequential(nn.Sequential):
 
 class UNetModel(nn.Module):
     """openaimodel3d.py:284-635 for the shipped DynamiCrafter-1024 configuration (configs/dynamicrafter/MotionRAG_open.yml:206-238)."""
+    frame_parallel = None          # set_frame_parallel
 
     def __init__(self, in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions, dropout=0.0, channel_mult=(1, 2, 4, 8),
                  conv_resample=True, dims=2, context_dim=None, use_scale_shift_norm=False, resblock_updown=False, num_heads=-1,
@@ -444,11 +499,20 @@ class UNetModel(nn.Module):
             raise NotImplementedError
         b, c, t, hh, ww = x.shape
         dev = x.device
+        fp, fr = _sharding(self), None
+        if fp is not None:                                             # this rank's frames only; the caller's tensors stay whole
+            fp.check(t, self._level_pixels(hh, ww))
+            fr = fp.frames(t)
+            x, t = x[:, :, fr.start:fr.stop], len(fr)
         mlp = lambda seq, e: ops.linear(ops.linear(e, seq[0].weight, seq[0].bias, epilogue=ops.EPI_SILU), seq[2].weight, seq[2].bias)
         emb = mlp(self.time_embed, ops.timestep_embedding(timesteps.to(dev, torch.float32), self.model_channels))      # :581-582
         ctx = {}
         if "image" in context:
-            ctx["image"] = context["image"].to(torch.bfloat16).reshape(b * t, -1, context["image"].shape[-1])            # 'b (t l) c -> (b t) l c'
+            if fr is None:
+                ctx["image"] = context["image"].to(torch.bfloat16).reshape(b * t, -1, context["image"].shape[-1])        # 'b (t l) c -> (b t) l c'
+            else:
+                img = context["image"].to(torch.bfloat16)
+                ctx["image"] = img.reshape(b, t * fp.world, -1, img.shape[-1])[:, fr.start:fr.stop].reshape(b * t, -1, img.shape[-1])
         if "prompt" in context:
             ctx["prompt"] = context["prompt"].to(torch.bfloat16)       # repeated over t through kv_batch_div (no copy)  :590
         if "action" in context:
@@ -475,7 +539,18 @@ class UNetModel(nn.Module):
         N, H, W, C = h.shape
         go = self.out[0]
         y = conv3x3(ops.groupnorm(h.view(N, H * W, C), go.weight, go.bias, 32, go.eps, silu=True).view(N, H, W, C), self.out[2])
-        return y.view(b, t, H, W, -1).permute(0, 4, 1, 2, 3).contiguous()
+        y = y.view(b, t, H, W, -1)
+        if fp is not None:
+            y = fp.gather_frames(y)                                    # [b, t_all, H, W, c_out] on every rank
+        return y.permute(0, 4, 1, 2, 3).contiguous()
+
+    def _level_pixels(self, h: int, w: int) -> List[int]:
+        """pixels per frame at every resolution level (each Downsample is a stride-2, pad-1 3x3 convolution)"""
+        out = [h * w]
+        for _ in range(sum(isinstance(m, Downsample) for m in self.modules())):
+            h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+            out.append(h * w)
+        return out
 
 
 # ------------------------------------------------------------------------------------------------------ DDIM sampler

@@ -926,6 +926,11 @@ class TopkPlan:
 
 
 # ---------------------------------------------------------------------------------------------- UNet ops (channels-last rows)
+def _gn_chunks(N: int, HW: int) -> int:
+    """statistics chunks per sample of every GroupNorm form: >= ~2048 statistics workgroups even when N is 1 or 2"""
+    return max(1, min(1024, HW // 32, max(64, -(-2048 // N))))
+
+
 def groupnorm(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], groups: int, eps: float, *, silu: bool = False,
               emb: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, mod: Optional[torch.Tensor] = None,
               mod_geom: Optional[tuple] = None, fold: bool = False) -> torch.Tensor:
@@ -942,7 +947,7 @@ def groupnorm(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[tor
         out = torch.empty_like(x)
     elif out.shape != x.shape or out.stride(2) != 1 or out.stride(1) != C or (mod is None and not out.is_contiguous()):
         raise ValueError("groupnorm: out must have x's shape with contiguous rows")
-    chunks = max(1, min(1024, HW // 32, max(64, -(-2048 // N))))        # >= ~2048 statistics workgroups even when N is 1 or 2
+    chunks = _gn_chunks(N, HW)
     L = _lib.lib()
     ws = _attn_workspace(x.device, L.mrag_groupnorm_workspace_bytes(N, C, chunks), "gn")     # grow-only per (device, stream): no allocation per call
     a = GroupNormArgs()
@@ -962,6 +967,66 @@ def groupnorm(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[tor
         a.mod, a.mod_T, a.mod_H, a.mod_W, a.mod_Tz, a.mod_shift, a.mod_split = _p(mod), T, H, W, mod.shape[1], shift, 1 if split else 0
         a.y_stride_n = out.stride(0) if N > 1 else 0
     check(L.mrag_groupnorm_bf16(_stream(), ctypes.byref(a)), "mrag_groupnorm_bf16")
+    return out
+
+
+
+
+def _gn_split_args(x: torch.Tensor, groups: int):
+    from ._lib import GroupNormArgs
+    _dev(x, name="x")
+    if x.dim() != 3 or not x.is_contiguous():
+        raise ValueError("groupnorm: contiguous [N, HW, C] required")
+    N, HW, C = x.shape
+    chunks = _gn_chunks(N, HW)
+    ws = _attn_workspace(x.device, _lib.lib().mrag_groupnorm_split_workspace_bytes(N, C, chunks), "gn")
+    a = GroupNormArgs()
+    a.x, a.workspace = _p(x), _p(ws)
+    a.N, a.HW, a.C, a.G, a.chunks = N, HW, C, groups, chunks
+    return a
+
+
+def groupnorm_partial(x: torch.Tensor, groups: int, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [N, HW, C] bf16, ONE shard of a normalised extent -> fp32 [N, groups, 2]: (sum, sum of squares) per (n, group) of this shard
+    (mrag_groupnorm_partial_bf16).  The partials of all shards, stacked [W, N, groups, 2], go to `groupnorm_apply_stats`."""
+    a = _gn_split_args(x, groups)
+    if out is None:
+        out = torch.empty(x.shape[0], groups, 2, dtype=torch.float32, device=x.device)
+    elif out.shape != (x.shape[0], groups, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("groupnorm_partial: out must be contiguous fp32 [N, groups, 2] on x's device")
+    check(_lib.lib().mrag_groupnorm_partial_bf16(_stream(), ctypes.byref(a), _p(out)), "mrag_groupnorm_partial_bf16")
+    return out
+
+
+def groupnorm_apply_stats(x: torch.Tensor, partials: torch.Tensor, hw_total: int, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], groups: int,
+                          eps: float, *, silu: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """GroupNorm [+ SiLU] of the shard x [N, HW, C] with the statistics of ALL shards: `partials` fp32 [W, N, groups, 2] (folded in index order),
+    `hw_total` rows per sample over all shards (mrag_groupnorm_apply_stats_bf16).  W = 1, hw_total = HW: the bits of `groupnorm`."""
+    a = _gn_split_args(x, groups)
+    N = x.shape[0]
+    _dev(partials, torch.float32, name="partials")
+    if partials.dim() != 4 or tuple(partials.shape[1:]) != (N, groups, 2) or not partials.is_contiguous():
+        raise ValueError(f"groupnorm_apply_stats: partials {tuple(partials.shape)}: contiguous [W, {N}, {groups}, 2] expected")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or not out.is_contiguous():
+        raise ValueError("groupnorm_apply_stats: out must be contiguous with x's shape")
+    a.y, a.gamma, a.beta, a.silu, a.eps = _p(out), _p(gamma), _p(beta), 1 if silu else 0, eps
+    check(_lib.lib().mrag_groupnorm_apply_stats_bf16(_stream(), ctypes.byref(a), _p(partials), partials.shape[0], hw_total), "mrag_groupnorm_apply_stats_bf16")
+    return out
+
+
+def swap_outer(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [A, B, R] bf16 contiguous, R % 8 == 0 -> [B, A, R] contiguous: `x.permute(1, 0, 2).contiguous()` on the streaming copy kernel (mrag_swap_outer_bf16)"""
+    _dev(x, name="x")
+    if x.dim() != 3 or not x.is_contiguous():
+        raise ValueError("swap_outer: contiguous [A, B, R] required")
+    A, B, R = x.shape
+    if out is None:
+        out = torch.empty(B, A, R, dtype=x.dtype, device=x.device)
+    elif out.shape != (B, A, R) or not out.is_contiguous() or out.dtype != x.dtype:
+        raise ValueError("swap_outer: out must be contiguous [B, A, R]")
+    check(_lib.lib().mrag_swap_outer_bf16(_stream(), _p(x), _p(out), A, B, R), "mrag_swap_outer_bf16")
     return out
 
 
