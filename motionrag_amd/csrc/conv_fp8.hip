@@ -6,13 +6,11 @@
 //                   power-of-two exponent per INPUT pixel), W8 / ew from the same quantiser over the [Cout, 9 Cin] tap-major weight.
 //
 // Why a per-pixel exponent survives the gather: at Cin % 64 == 0 one MFMA k-step of 64 e4m3 lies inside ONE tap, and the instruction's E8M0 scale operand
-// applies per lane to that lane's own row's 32 k's (gemm_fp8.hip, operand maps).  So for every k-step a lane passes 127 - e of the SOURCE pixel its output
+// applies per lane to that lane's own row's 32 k's (gemm_fp8_tile.h, operand maps).  So for every k-step a lane passes 127 - e of the SOURCE pixel its output
 // row reads under that step's tap.  A padded tap gathers zero bytes; its scale is immaterial.
 //
-// Kernel shape: gemm_fp8_kernel's -- a 256x256 tile on 8 waves (2 x 4, 128 rows x 64 columns each), two LDS stages of 64 KiB filled by 16-byte
-// global_load_lds in 1-KiB pieces with the XOR swizzle on the source address, hand-written fragment reads under counted lgkmcnt, the DMA of K-tile t + 1
-// issued behind the barrier that opens tile t and retired by the vmcnt(0) in front of the next barrier, the LDS-staged epilogue -- with the tap walk and
-// the border predicate of gemm_tile.h's CONV == 1 addressing on the activation operand.
+// Kernel shape: the e4m3 256x256 tile of gemm_fp8_tile.h (shared with gemm_fp8_kernel: stages, fragment reads, k-step schedule, staged epilogue) with the
+// tap walk and the border predicate of gemm_tile.h's CONV == 1 addressing on the activation operand.
 // K-tile: 128 bytes = TWO 64-channel steps, each a whole step of one tap, addressed independently.  A DMA lane moves one 16-byte chunk of one step
 // (logical chunk c of its row: step c >> 2), so it walks ITS step's (tap, channel block) and the two halves of a K-tile may lie in different taps
 // (Cin = 320: five steps per tap, 45 steps, the tap changes in the middle of every fifth tile).  This keeps the LDS image, the two-step fragment schedule
@@ -23,7 +21,7 @@
 // hand-written ds_read_b32 in front of the fragment reads, so nothing inside the MFMA loop touches vmcnt but the DMA.
 // Source offsets are 32-bit: activations in bytes relative to the first sample a workgroup touches, weight rows in bytes relative to W (mrag_conv_fp8
 // returns MRAG_ENOTSUP past them: the guard of mrag_conv_bf16 restated for bytes).
-#include "gemm_common.h"
+#include "gemm_fp8_tile.h"
 
 // host-side relaxed launch counter (mrag_conv_fp8_launch_counts): slot 0 the convolution
 static unsigned long long g_conv8_launches[1];
@@ -40,29 +38,21 @@ struct Conv8P {
   int tiles_m, tiles_n, group_m, wide;
 };
 
-constexpr int C8_BM = 256, C8_BN = 256, C8_BK = 128;        // BK in bytes == e4m3 elements: two 64-channel steps
-constexpr int C8_STAGE = (C8_BM + C8_BN) * C8_BK;          // 64 KiB
-constexpr int C8_ROWB = 144;                               // staged epilogue: row pitch of a wave's 128 x 64 bf16 tile
-constexpr int C8_SC_OFF = 8 * 128 * C8_ROWB;               // 144 KiB: the scale words sit behind the epilogue's per-wave regions (which overlay the stages)
+constexpr int C8_SC_OFF = F8_EPI_LDS;                     // 144 KiB: the scale words sit behind the epilogue's per-wave regions (which overlay the stages)
 constexpr int C8_SC_TAPS = 10;                             // nine taps + the dead step's row (scale 1)
 constexpr int C8_LDS = C8_SC_OFF + C8_SC_TAPS * 2 * 32 * 4;
-static_assert(C8_SC_OFF >= 2 * C8_STAGE && C8_LDS <= 160 * 1024, "stages, epilogue region and scale words fit the CU's LDS");
+static_assert(C8_LDS <= 160 * 1024, "stages, epilogue region and scale words fit the CU's LDS");
 
 template <int EPI>
 __global__ __launch_bounds__(512) void conv_fp8_kernel(const Conv8P p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int NW = 8, APW = C8_BM / 8 / NW, WPW = C8_BN / 8 / NW;   // 64 pieces of 1 KiB per stage, 8 per wave: the first 4 are activation rows, the others W rows
+  constexpr int NW = 8, APW = F8_BM / 8 / NW, WPW = F8_BN / 8 / NW;   // 64 pieces of 1 KiB per stage, 8 per wave: the first 4 are activation rows, the others W rows
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 2, wn = wave & 3;
   const int r32 = lane & 31, hh = lane >> 5;
 
-  // logical tile order of gemm_tile.h: groups of group_m m-tiles walked n-major behind the XCD remap
-  const int wg = xcd_remap(blockIdx.x, gridDim.x);
-  const int gw = p.group_m * p.tiles_n;
-  const int first_m = (wg / gw) * p.group_m;
-  const int gsz = min(p.tiles_m - first_m, p.group_m);
-  const int tile_m = first_m + (wg % gw) % gsz, tile_n = (wg % gw) / gsz;
-  const long long bm0 = (long long)tile_m * C8_BM, bn0 = (long long)tile_n * C8_BN;
+  long long bm0, bn0;
+  fp8_tile_origin(p.tiles_m, p.tiles_n, p.group_m, bm0, bn0);
 
   const int HW = p.H * p.Wd;
   const long long n0 = bm0 / HW;                                       // the first sample this workgroup touches
@@ -70,7 +60,7 @@ __global__ __launch_bounds__(512) void conv_fp8_kernel(const Conv8P p) {
 
   // ---- scale words: thread t < 256 owns output row bm0 + t and writes, per tap, the byte 127 - e of the pixel that row reads under the tap
   // (word [(tap, t >> 7, t & 31)], byte (t >> 5) & 3: the row block inside the wave's 128 rows)
-  if (tid < C8_BM) {
+  if (tid < F8_BM) {
     unsigned char* sc = (unsigned char*)(smem + C8_SC_OFF) + (((tid >> 7) * 32 + (tid & 31)) << 2) + ((tid >> 5) & 3);
     long long row = bm0 + tid;
     row = row < p.M ? row : p.M - 1;
@@ -116,7 +106,7 @@ __global__ __launch_bounds__(512) void conv_fp8_kernel(const Conv8P p) {
   const int ct = p.ctiles;
   int ls = hs, ltap = (hs && ct == 1) ? 1 : 0, lcb = (hs && ct != 1) ? 1 : 0;
   auto issue = [&](int stage) {
-    char* base = smem + stage * C8_STAGE;
+    char* base = smem + stage * F8_STAGE;
     const bool live = ls < p.steps;
     const unsigned hlim = live ? (unsigned)p.H : 0u;                   // a dead step (odd 9 Cin / 64: the last tile's second half) gathers zeros
     const int ky = ltap / 3, kx = ltap - 3 * ky;
@@ -136,58 +126,19 @@ __global__ __launch_bounds__(512) void conv_fp8_kernel(const Conv8P p) {
     if (lcb >= ct) { lcb -= ct; ++ltap; }
   };
 
-  // E8M0 scale operands of the W rows (A operand): the lane's row of both 32-column blocks
   int sw[2];
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    long long n = bn0 + wn * 64 + j * 32 + r32;
-    n = n < p.N ? n : p.N - 1;
-    sw[j] = ((127 - p.ew[n]) & 0xff) * 0x01010101;
-  }
-
-  f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // fragment read addresses: row r32 of a 32-row block (pitch 4096), bytes 32 hh .. + 31 of the 64-byte k-step as two 16-byte chunks, un-swizzled by row & 7
+  for (int j = 0; j < 2; ++j) sw[j] = fp8_row_scale(p.ew, bn0 + wn * 64 + j * 32 + r32, p.N);
+  f32x16 acc[4][2] = {};
+  // fragment read addresses: the lane's first activation / W row in stage 0, its scale word under tap 0, and its chunks' offsets inside a row
   const unsigned smem_u = (unsigned)(size_t)smem;
-  const int swz = r32 & 7;
-  const unsigned rowA = smem_u + (wm * 128 + r32) * 128, rowW = smem_u + C8_BM * 128 + (wn * 64 + r32) * 128;
+  const unsigned rowA = smem_u + (wm * 128 + r32) * 128, rowW = smem_u + F8_BM * 128 + (wn * 64 + r32) * 128;
   const unsigned scA = smem_u + C8_SC_OFF + ((wm * 32 + r32) << 2);     // + 256 tap: the word of this lane's rows under that tap
-  unsigned ca[2][2];                                         // [k-step][half]: byte offset of the chunk inside the row
+  unsigned ca[2][2];                                         // [k-step][half]
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-    for (int c = 0; c < 2; ++c) ca[ks][c] = (unsigned)(((4 * ks + 2 * hh + c) ^ swz) << 4);
-
-  // the scale word, then twelve fragment reads of one k-step (W blocks first), released by counted lgkmcnt (LDS reads return in order)
-#define MRAG8_READ13(S, W, A, AS, AW0, AW1, AA0, AA1)                                                               \
-  asm volatile(                                                                                                     \
-      "ds_read_b32 %12, %17\n\t"                                                                                    \
-      "ds_read_b128 %0, %13\n\tds_read_b128 %1, %14\n\tds_read_b128 %2, %13 offset:4096\n\tds_read_b128 %3, %14 offset:4096\n\t" \
-      "ds_read_b128 %4, %15\n\tds_read_b128 %5, %16\n\tds_read_b128 %6, %15 offset:4096\n\tds_read_b128 %7, %16 offset:4096\n\t" \
-      "ds_read_b128 %8, %15 offset:8192\n\tds_read_b128 %9, %16 offset:8192\n\tds_read_b128 %10, %15 offset:12288\n\tds_read_b128 %11, %16 offset:12288" \
-      : "=&v"(W[0]), "=&v"(W[1]), "=&v"(W[2]), "=&v"(W[3]), "=&v"(A[0]), "=&v"(A[1]), "=&v"(A[2]), "=&v"(A[3]),      \
-        "=&v"(A[4]), "=&v"(A[5]), "=&v"(A[6]), "=&v"(A[7]), "=&v"(S)                                               \
-      : "v"(AW0), "v"(AW1), "v"(AA0), "v"(AA1), "v"(AS)                                                             \
-      : "memory")
-  // the wait names the registers it releases ("+v"): the MFMAs that read them cannot be scheduled in front of it
-#define MRAG8_WAIT_SWA(N, S, W, A0, A1)                                                                              \
-  asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(S), "+v"(W[0]), "+v"(W[1]), "+v"(W[2]), "+v"(W[3]), "+v"(A0), "+v"(A1) :: "memory")
-#define MRAG8_WAIT_A(N, A0, A1) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(A0), "+v"(A1) :: "memory")
-#define MRAG8_FRAG(X, Y) (i32x8{(int)X[0], (int)X[1], (int)X[2], (int)X[3], (int)Y[0], (int)Y[1], (int)Y[2], (int)Y[3]})
-  // row block I: its scale byte of the word replicated (v_perm_b32), as gemm_fp8_kernel passes its row scales
-#define MRAG8_ROW(I, S, W, A0, A1)                                                                                   \
-  do {                                                                                                              \
-    const i32x8 af = MRAG8_FRAG(A0, A1);                                                                            \
-    const int sa = (int)__builtin_amdgcn_perm(S, S, 0x01010101u * (I));                                             \
-    acc[I][0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(MRAG8_FRAG(W[0], W[1]), af, acc[I][0], 0, 0, 0, sw[0], 0, sa); \
-    acc[I][1] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(MRAG8_FRAG(W[2], W[3]), af, acc[I][1], 0, 0, 0, sw[1], 0, sa); \
-  } while (0)
+    for (int c = 0; c < 2; ++c) ca[ks][c] = fp8_frag_chunk(ks, hh, c, r32);
 
   // the tap of the two steps of the K-tile being multiplied (workgroup-uniform walk, as the lanes' above)
   int ut[2] = {0, ct == 1 ? 1 : 0}, uc[2] = {0, ct == 1 ? 0 : 1};
@@ -196,41 +147,22 @@ __global__ __launch_bounds__(512) void conv_fp8_kernel(const Conv8P p) {
   issue(0);
   for (int kt = 0; kt < p.nk; ++kt) {
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");   // tile kt landed for every wave; every wave finished reading the other stage
-    const unsigned so = (unsigned)((kt & 1) * C8_STAGE);
+    const unsigned so = (unsigned)((kt & 1) * F8_STAGE);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      u32x4 w[4], a[8];
-      unsigned s;
-      MRAG8_READ13(s, w, a, scA + (unsigned)(ut[ks] << 8), rowW + so + ca[ks][0], rowW + so + ca[ks][1], rowA + so + ca[ks][0], rowA + so + ca[ks][1]);
+      Fp8Frag f;
+      fp8_tile_read<true>(f, rowW + so + ca[ks][0], rowW + so + ca[ks][1], rowA + so + ca[ks][0], rowA + so + ca[ks][1], scA + (unsigned)(ut[ks] << 8));
       if (ks == 0 && kt + 1 < p.nk) issue((kt + 1) & 1);            // the next tile's eight DMA requests go out under the first fragments' LDS latency
-      // the order below is the schedule (hipcc would gather the four waits in front of the first MFMA): each pair of MFMAs starts when ITS rows are here
-      __builtin_amdgcn_sched_barrier(0);
-      MRAG8_WAIT_SWA(6, s, w, a[0], a[1]);
-      MRAG8_ROW(0, s, w, a[0], a[1]);
-      __builtin_amdgcn_sched_barrier(0);
-      MRAG8_WAIT_A(4, a[2], a[3]);
-      MRAG8_ROW(1, s, w, a[2], a[3]);
-      __builtin_amdgcn_sched_barrier(0);
-      MRAG8_WAIT_A(2, a[4], a[5]);
-      MRAG8_ROW(2, s, w, a[4], a[5]);
-      __builtin_amdgcn_sched_barrier(0);
-      MRAG8_WAIT_A(0, a[6], a[7]);
-      MRAG8_ROW(3, s, w, a[6], a[7]);
-      __builtin_amdgcn_sched_barrier(0);
+      fp8_tile_mfma<true>(acc, f, sw);
       uc[ks] += 2;
       if (uc[ks] >= ct) { uc[ks] -= ct; ++ut[ks]; }
       if (uc[ks] >= ct) { uc[ks] -= ct; ++ut[ks]; }
     }
   }
-#undef MRAG8_READ13
-#undef MRAG8_WAIT_SWA
-#undef MRAG8_WAIT_A
-#undef MRAG8_FRAG
-#undef MRAG8_ROW
 
-  // ---- epilogue, LDS-staged as in gemm_fp8_kernel: the wave's 128 x 64 bf16 tile goes through LDS (row pitch 144 B) and leaves as whole row segments;
-  // bias in the accumulator layout, rounded to bf16, the residual added in the row layout (so y may alias resid: a lane reads what it overwrites first)
-  char* wbase = smem + wave * (128 * C8_ROWB);
+  // ---- epilogue, LDS-staged (gemm_fp8_tile.h): bias in the accumulator layout, rounded to bf16, the residual added in the row layout (so y may alias
+  // resid: a lane reads what it overwrites first)
+  char* wbase = smem + wave * (128 * F8_ROWB);
   __syncthreads();   // every wave is done with the operand stages that these per-wave regions overlay (no DMA is in flight: the last tile issued none)
   // (the lane's eight bias quads depend on the column only: loaded once, in one memory latency, not per row block)
   float bv[2][4][4];
@@ -242,8 +174,7 @@ __global__ __launch_bounds__(512) void conv_fp8_kernel(const Conv8P p) {
       n = n < p.N ? n : p.N - 4;   // clamped columns are never stored
       u32x2 bb = u32x2{0u, 0u};
       if (p.bias) bb = *(const u32x2*)(p.bias + n);
-      bv[j][g][0] = __uint_as_float(bb[0] << 16); bv[j][g][1] = __uint_as_float(bb[0] & 0xffff0000u);
-      bv[j][g][2] = __uint_as_float(bb[1] << 16); bv[j][g][3] = __uint_as_float(bb[1] & 0xffff0000u);
+      fp8_unpack_bf4(bb, bv[j][g]);
     }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -256,7 +187,7 @@ __global__ __launch_bounds__(512) void conv_fp8_kernel(const Conv8P p) {
         u32x2 out;
         out[0] = pack_bf2(acc[i][j][4 * g] + bv[j][g][0], acc[i][j][4 * g + 1] + bv[j][g][1]);
         out[1] = pack_bf2(acc[i][j][4 * g + 2] + bv[j][g][2], acc[i][j][4 * g + 3] + bv[j][g][3]);
-        *(u32x2*)(wbase + lrow * C8_ROWB + lcol * 2) = out;
+        *(u32x2*)(wbase + lrow * F8_ROWB + lcol * 2) = out;
       }
     }
   }
@@ -288,16 +219,8 @@ __global__ __launch_bounds__(512) void conv_fp8_kernel(const Conv8P p) {
 #pragma unroll
   for (int g = 0; g < 16; ++g) {
     const long long m = m0 + g * 8;
-    u32x4 val = *(const u32x4*)(wbase + (g * 8 + rsub) * C8_ROWB + ch * 16);
-    if constexpr (EPI == MRAG_EPI_RESID) {
-      const u32x4 rr = rpre[g];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float lo = __uint_as_float(val[e] << 16) + __uint_as_float(rr[e] << 16);
-        const float hi = __uint_as_float(val[e] & 0xffff0000u) + __uint_as_float(rr[e] & 0xffff0000u);
-        val[e] = pack_bf2(lo, hi);
-      }
-    }
+    u32x4 val = *(const u32x4*)(wbase + (g * 8 + rsub) * F8_ROWB + ch * 16);
+    if constexpr (EPI == MRAG_EPI_RESID) val = fp8_add_bf8(val, rpre[g]);
     if (m < p.M) {
       bf16_t* q = p.Y + m * p.N + n;
       if (p.wide) {
@@ -335,7 +258,7 @@ extern "C" int mrag_conv_fp8(void* stream, const mrag_conv_fp8_args* a) {
   const long long HW = (long long)a->H * a->Wd, M = (long long)a->N * HW;
   if (a->H > 32767 || a->Wd > 32767 || M > 0x7fffffffll) return MRAG_ENOTSUP;
   if ((255 / HW + 2) * HW * a->Cin >= (1LL << 31) || (long long)a->Cout * 9 * a->Cin >= (1LL << 32)) return MRAG_ENOTSUP;
-  const long long tiles_m = (M + C8_BM - 1) / C8_BM, tiles_n = ((long long)a->Cout + C8_BN - 1) / C8_BN;
+  const long long tiles_m = (M + F8_BM - 1) / F8_BM, tiles_n = ((long long)a->Cout + F8_BN - 1) / F8_BN;
   if (tiles_m * tiles_n > 0x7fffffffll) return MRAG_ENOTSUP;
   Conv8P p{};
   p.X = (const uint8_t*)a->x8; p.W = (const uint8_t*)a->W8; p.ex = a->x_exp; p.ew = a->w_exp;

@@ -494,6 +494,34 @@ def quant_rows_e4m3(x: torch.Tensor, out: Optional[tuple] = None):
     return x8, ex
 
 
+def _fp8_rows_workspace(device: torch.device, M: int, K: int, kind: str):
+    """(x8 [M, K] uint8, exp [M] int32) inside the grow-only workspace `kind` of the (device, stream)"""
+    exp_bytes = (M * 4 + 255) // 256 * 256
+    ws = _attn_workspace(device, exp_bytes + M * K, kind)
+    return ws[exp_bytes:exp_bytes + M * K].view(M, K), ws[:M * 4].view(torch.int32)
+
+
+def _fp8_gemm_args(name: str, K: int, w8: torch.Tensor, w_exp: torch.Tensor, bias: Optional[torch.Tensor], epilogue: int) -> GemmFp8Args:
+    """the (w8, w_exp) / bias checks of `linear_fp8` and `linear_fp8_k64` (raising under `name`) -> their GemmFp8Args with the weight half filled"""
+    _dev(w8, torch.uint8, "w8"); _dev(w_exp, torch.int32, "w_exp")
+    if bias is not None:
+        _dev(bias, name="bias")
+    N = w8.shape[0]
+    if w8.dim() != 2 or w8.shape[1] != K or w8.stride(1) != 1 or tuple(w_exp.shape) != (N,) or not w_exp.is_contiguous():
+        raise ValueError(f"{name}: w8 {tuple(w8.shape)} / w_exp {tuple(w_exp.shape)} do not match K={K}")
+    a = GemmFp8Args()
+    a.W8, a.w_exp, a.bias, a.N, a.K, a.ldw, a.epilogue = _p(w8), _p(w_exp), _p(bias), N, K, w8.stride(0), epilogue
+    return a
+
+
+def _fp8_gemm_launch(entry: str, a: GemmFp8Args, a8: torch.Tensor, a_exp: torch.Tensor, o2: torch.Tensor, r2: Optional[torch.Tensor]) -> None:
+    """the activation / output half of `a` (a8, o2 and r2 as rows) and the launch of mrag_gemm_fp8 or mrag_gemm_fp8_k64"""
+    a.A8, a.a_exp, a.C, a.M, a.lda, a.ldc = _p(a8), _p(a_exp), _p(o2), a8.shape[0], a8.stride(0), o2.stride(0)
+    if r2 is not None:
+        a.resid, a.ldr = _p(r2), r2.stride(0)
+    check(getattr(_lib.lib(), entry)(_stream(), ctypes.byref(a)), entry)
+
+
 def linear_fp8(x: torch.Tensor, w8: torch.Tensor, w_exp: torch.Tensor, bias: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None,
                epilogue: int = EPI_NONE, resid: Optional[torch.Tensor] = None, gate0: Optional[torch.Tensor] = None,
                gate1: Optional[torch.Tensor] = None, rows_per_batch: int = 0, split: int = 0, gate_stride: int = 0) -> torch.Tensor:
@@ -501,37 +529,24 @@ def linear_fp8(x: torch.Tensor, w8: torch.Tensor, w_exp: torch.Tensor, bias: Opt
     (w8, w_exp) = quant_rows_e4m3(weight) is the weight quantised once per output channel.  Epilogues EPI_NONE / EPI_GELU_TANH / EPI_RESID /
     EPI_GATE_RESID as in `linear` (out may be resid).  Two launches, nothing read back: capturable into a HIP graph.  Raises on shapes the kernel
     does not take (`fp8_linear_supported`): opting in is explicit, so is its refusal."""
-    _dev(x, name="x"); _dev(w8, torch.uint8, "w8"); _dev(w_exp, torch.int32, "w_exp")
-    if bias is not None:
-        _dev(bias, name="bias")
-    x2 = _rows(x)
+    x2 = _rows(_dev(x, name="x"))
     M, K = x2.shape
-    N = w8.shape[0]
-    if w8.dim() != 2 or w8.shape[1] != K or w8.stride(1) != 1 or tuple(w_exp.shape) != (N,) or not w_exp.is_contiguous():
-        raise ValueError(f"linear_fp8: w8 {tuple(w8.shape)} / w_exp {tuple(w_exp.shape)} do not match K={K}")
+    a = _fp8_gemm_args("linear_fp8", K, w8, w_exp, bias, epilogue)
+    N = a.N
     if not fp8_linear_supported(N, K):
         raise ValueError(f"linear_fp8: N={N}, K={K} outside the fp8 GEMM's shapes (K % 128 == 0, N % 16 == 0)")
     if epilogue not in (EPI_NONE, EPI_GELU_TANH, EPI_RESID, EPI_GATE_RESID):
         raise ValueError(f"linear_fp8: epilogue {epilogue} does not exist on the fp8 GEMM")
-    exp_bytes = (M * 4 + 255) // 256 * 256
-    ws = _attn_workspace(x.device, exp_bytes + M * K, "fp8lin")
-    a_exp, a8 = ws[:M * 4].view(torch.int32), ws[exp_bytes:exp_bytes + M * K].view(M, K)
+    a8, a_exp = _fp8_rows_workspace(x.device, M, K, "fp8lin")
     quant_rows_e4m3(x2, out=(a8, a_exp))
     if out is None:
         out = torch.empty(*x.shape[:-1], N, dtype=torch.bfloat16, device=x.device)
     o2 = _rows(_dev(out, name="out"))
-    a = GemmFp8Args()
-    a.A8, a.W8, a.a_exp, a.w_exp, a.bias, a.C = _p(a8), _p(w8), _p(a_exp), _p(w_exp), _p(bias), _p(o2)
-    a.M, a.N, a.K = M, N, K
-    a.lda, a.ldw, a.ldc = a8.stride(0), w8.stride(0), o2.stride(0)
-    a.epilogue = epilogue
-    if resid is not None:
-        r2 = _rows(_dev(resid, name="resid"))
-        a.resid, a.ldr = _p(r2), r2.stride(0)
+    r2 = _rows(_dev(resid, name="resid")) if resid is not None else None
     if epilogue == EPI_GATE_RESID:
         a.gate0, a.gate1 = _p(_dev(gate0, name="gate0")), _p(_dev(gate1, name="gate1"))
         a.rows_per_batch, a.split, a.gate_stride = rows_per_batch, split, gate_stride
-    check(_lib.lib().mrag_gemm_fp8(_stream(), ctypes.byref(a)), "mrag_gemm_fp8")
+    _fp8_gemm_launch("mrag_gemm_fp8", a, a8, a_exp, o2, r2)
     return out
 
 
@@ -548,13 +563,6 @@ def fp8_linear_k64_supported(N: int, K: int, epilogue: int = EPI_NONE) -> bool:
     if epilogue not in (EPI_NONE, EPI_RESID, EPI_GEGLU):
         return False
     return N > 0 and K > 0 and K % 64 == 0 and N % (32 if epilogue == EPI_GEGLU else 16) == 0
-
-
-def _fp8_rows_workspace(device: torch.device, M: int, K: int, kind: str):
-    """(x8 [M, K] uint8, exp [M] int32) inside the grow-only workspace `kind` of the (device, stream)"""
-    exp_bytes = (M * 4 + 255) // 256 * 256
-    ws = _attn_workspace(device, exp_bytes + M * K, kind)
-    return ws[exp_bytes:exp_bytes + M * K].view(M, K), ws[:M * 4].view(torch.int32)
 
 
 def layernorm_e4m3(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], eps: float):
@@ -580,9 +588,6 @@ def linear_fp8_k64(x, w8: torch.Tensor, w_exp: torch.Tensor, bias: Optional[torc
     (w8, w_exp and bias in `geglu_interleave`'s row order; out [M, N / 2]).  `x` is bf16 rows [..., K], quantised per row in front of the launch into a
     grow-only workspace, or an already quantised pair (x8 [M, K] uint8, exp [M] int32) such as `layernorm_e4m3` returns (out is then [M, n]).
     Nothing read back: capturable into a HIP graph.  Raises on what the kernel does not take (`fp8_linear_k64_supported`)."""
-    _dev(w8, torch.uint8, "w8"); _dev(w_exp, torch.int32, "w_exp")
-    if bias is not None:
-        _dev(bias, name="bias")
     if isinstance(x, (tuple, list)):
         a8, a_exp = x
         _dev(a8, torch.uint8, "x8"); _dev(a_exp, torch.int32, "exp")
@@ -595,9 +600,8 @@ def linear_fp8_k64(x, w8: torch.Tensor, w_exp: torch.Tensor, bias: Optional[torc
         x2 = _rows(x)
         lead = tuple(x.shape[:-1])
         M, K = x2.shape
-    N = w8.shape[0]
-    if w8.dim() != 2 or w8.shape[1] != K or w8.stride(1) != 1 or tuple(w_exp.shape) != (N,) or not w_exp.is_contiguous():
-        raise ValueError(f"linear_fp8_k64: w8 {tuple(w8.shape)} / w_exp {tuple(w_exp.shape)} do not match K={K}")
+    a = _fp8_gemm_args("linear_fp8_k64", K, w8, w_exp, bias, epilogue)
+    N = a.N
     if not fp8_linear_k64_supported(N, K, epilogue):
         raise ValueError(f"linear_fp8_k64: N={N}, K={K}, epilogue {epilogue} outside the kernel's shapes (K % 64 == 0, N % 16 == 0, GEGLU N % 32 == 0; "
                          "EPI_NONE / EPI_RESID / EPI_GEGLU)")
@@ -612,17 +616,10 @@ def linear_fp8_k64(x, w8: torch.Tensor, w_exp: torch.Tensor, bias: Optional[torc
     o2 = _rows(_dev(out, name="out"))
     if tuple(o2.shape) != (M, ncols):
         raise ValueError(f"linear_fp8_k64: out {tuple(out.shape)} is not [{M}, {ncols}]")
-    a = GemmFp8Args()
-    a.A8, a.W8, a.a_exp, a.w_exp, a.bias, a.C = _p(a8), _p(w8), _p(a_exp), _p(w_exp), _p(bias), _p(o2)
-    a.M, a.N, a.K = M, N, K
-    a.lda, a.ldw, a.ldc = a8.stride(0), w8.stride(0), o2.stride(0)
-    a.epilogue = epilogue
-    if resid is not None:
-        r2 = _rows(_dev(resid, name="resid"))
-        if tuple(r2.shape) != (M, N):
-            raise ValueError(f"linear_fp8_k64: resid {tuple(resid.shape)} is not [{M}, {N}]")
-        a.resid, a.ldr = _p(r2), r2.stride(0)
-    check(_lib.lib().mrag_gemm_fp8_k64(_stream(), ctypes.byref(a)), "mrag_gemm_fp8_k64")
+    r2 = _rows(_dev(resid, name="resid")) if resid is not None else None
+    if r2 is not None and tuple(r2.shape) != (M, N):
+        raise ValueError(f"linear_fp8_k64: resid {tuple(resid.shape)} is not [{M}, {N}]")
+    _fp8_gemm_launch("mrag_gemm_fp8_k64", a, a8, a_exp, o2, r2)
     return out
 
 
@@ -1122,9 +1119,7 @@ def conv_implicit_fp8(x: torch.Tensor, w8: torch.Tensor, w_exp: torch.Tensor, bi
     if not conv_fp8_supported(N, H, W, C, cout):
         raise ValueError(f"conv_implicit_fp8: {tuple(x.shape)} -> {cout} channels is outside the fp8 convolution's shapes")
     M = N * H * W
-    exp_bytes = (M * 4 + 255) // 256 * 256
-    ws = _attn_workspace(x.device, exp_bytes + M * C, "fp8conv")
-    x_exp, x8 = ws[:M * 4].view(torch.int32), ws[exp_bytes:exp_bytes + M * C].view(M, C)
+    x8, x_exp = _fp8_rows_workspace(x.device, M, C, "fp8conv")
     quant_rows_e4m3(x.view(M, C), out=(x8, x_exp))
     if out is None:
         out = torch.empty(N, H, W, cout, dtype=torch.bfloat16, device=x.device)

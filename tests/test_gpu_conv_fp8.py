@@ -214,7 +214,39 @@ def test_conv_fp8_gate_matches_the_c_entry_point(hip):
         ops.conv_implicit_fp8(torch.zeros(1, 4, 4, 96, dtype=torch.bfloat16, device=DEV), buf[:16 * 864].view(16, 864), torch.zeros(16, dtype=torch.int32, device=DEV), None)
 
 
-# ---------------------------------------------------------------------------------------------------------------- 4. models
+# ---------------------------------------------------------------------------------------------------------------- 4. one tile with the fp8 GEMM
+@pytest.mark.parametrize("epi", [EPI_NONE, EPI_RESID], ids=["none", "resid"])
+@pytest.mark.parametrize("n,cin,cout", [(300, 64, 320),     # 9 steps: the dead last half-tile, two row tiles, two column tiles, ragged both ways
+                                        (257, 128, 48)],    # 18 steps: both halves live, and the GEMM's two-step tile
+                         ids=["300x64x320", "257x128x48"])
+def test_conv_fp8_on_1x1_images_is_the_fp8_gemm(hip, n, cin, cout, epi):
+    """mrag_conv_fp8 and mrag_gemm_fp8_k64 run one tile (csrc/gemm_fp8_tile.h): on 1x1 images the convolution is the GEMM, bit for bit.  With H = W = 1
+    eight taps gather zero bytes, so the accumulator receives exact zeros around the centre tap's Cin / 64 k-steps: the MFMA steps, in the order, of the GEMM
+    on A8 = x8, a_exp = x_exp and W8 = the centre-tap column slice w8[:, 4 Cin : 5 Cin] (row stride 9 Cin, 16-byte aligned) with the same w_exp.  Bias and
+    residual have the same rounding points in both epilogues."""
+    from motionrag_amd import _lib, ops
+    from test_gpu_ff_fp8 import _c_gemm
+    g = torch.Generator().manual_seed(n + cin + cout)
+    x = bf(torch.randn(n, cin, generator=g) * torch.exp2(torch.randint(-6, 7, (n, 1), generator=g).float())).to(DEV)
+    w = bf(torch.randn(cout, 9 * cin, generator=g) * cin ** -0.5).to(DEV)
+    bias = bf(torch.randn(cout, generator=g)).to(DEV)
+    resid = bf(torch.randn(n, cout, generator=g) * 4).to(DEV) if epi == EPI_RESID else None
+    x8, x_exp = ops.quant_rows_e4m3(x)
+    w8, w_exp = ops.quant_rows_e4m3(w)
+    conv = torch.empty(n, cout, dtype=torch.bfloat16, device=DEV)
+    a = _lib.ConvFp8Args()
+    a.x8, a.W8, a.x_exp, a.w_exp, a.bias, a.y = x8.data_ptr(), w8.data_ptr(), x_exp.data_ptr(), w_exp.data_ptr(), bias.data_ptr(), conv.data_ptr()
+    a.N, a.H, a.Wd, a.Cin, a.Cout, a.stride, a.epilogue = n, 1, 1, cin, cout, 1, epi
+    if resid is not None:
+        a.resid = resid.data_ptr()
+    _lib.check(hip.mrag_conv_fp8(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), ctypes.byref(a)), "mrag_conv_fp8")
+    gemm = _c_gemm(hip.mrag_gemm_fp8_k64, x8, x_exp, w8[:, 4 * cin:5 * cin], w_exp, bias, epi, resid)
+    assert torch.equal(conv, gemm), (conv.float() - gemm.float()).abs().max()
+    product = gemm.float() - bias.float() - (resid.float() if resid is not None else 0.0)
+    assert torch.isfinite(gemm.float()).all() and product.abs().mean() > 0.05, product.abs().mean()   # the centre tap's product is in the result
+
+
+# ---------------------------------------------------------------------------------------------------------------- 5. models
 def _emulating_conv3x3(real, log):
     """layers.conv3x3 with the host emulation in place of the gated convolutions (the others run as they are)"""
     from motionrag_amd import ops
