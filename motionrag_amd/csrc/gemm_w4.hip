@@ -3,6 +3,21 @@
 
 namespace {
 
+// the lane id, re-derived where it is needed from the (full: every branch around a caller is wave-uniform) exec mask.  volatile asm: hipcc neither hoists it
+// out of the tile loop nor keeps a copy of the kernel's own lane id live across the K loop for it (such a copy is spilled around the loop)
+__device__ __forceinline__ int lane_id_here() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+// a masked (so provably non-negative) lane-derived index on its way into 64-bit pointer arithmetic: hipcc zero-extends it into a register pair whose high half, a
+// constant 0, it defines once in front of the tile loop -- the pair is then live across the K loop and spilled around it.  Behind this the sign is unknown and the
+// high half is made where the low half is (one shift per tile)
+__device__ __forceinline__ int opaque_sign(int x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
 // ---- the four-wave kernel's epilogue: 128x128 per wave.
 // Fast path (the wave's 128 x 128 outputs all inside the matrix, 16-byte aligned rows, one gate vector for the whole wave tile -- every tile of the DiT but
 // the last row of tiles): sixteen rows at a time go from the accumulator layout (lane: row (lane & 15), columns (lane >> 4) * 4 + {0..3} of every 16x16
@@ -17,15 +32,13 @@ namespace {
 // General path (edge tiles, a sample or text / video boundary inside the wave's rows, unaligned C): 8-byte predicated stores from the accumulator layout.
 template <int EPI>
 __device__ __forceinline__ void epilogue_w4(const GemmP& p, char* smem, f32x4 (&acc)[8][8], const long long bm0, const long long bn0, const int wave, const int wrow0,
-                                            const int wcol0, const int lane_in, const long long Mend) {   // Mend: rows [.., Mend) exist (p.M, or the end of the tile's sample)
+                                            const int wcol0, const long long Mend) {   // Mend: rows [.., Mend) exist (p.M, or the end of the tile's sample)
   constexpr bool HAS_R = (EPI == MRAG_EPI_GATE_RESID || EPI == MRAG_EPI_RESID), HAS_G = (EPI == MRAG_EPI_GATE_RESID), QK = (EPI == MRAG_EPI_QKNORM_ROPE);
-  // the lane id is laundered through an empty asm: everything below that depends on the lane only (LDS addresses, column offsets, row pointers) would
+  // the lane id comes from a volatile asm: everything below that depends on the lane only (LDS addresses, column offsets, row pointers) would
   // otherwise be hoisted out of the tile loop and kept in registers ACROSS the K loop, whose 128 fragment registers leave no room -- hipcc then spills
   // around the loop and parks the reload's `s_waitcnt vmcnt(0)` in the loop header, which drains the DMA ring once per K-tile (measured: +33 % K-loop time)
-  int lane_e = lane_in;
-  asm volatile("" : "+v"(lane_e));
-  const int lane = lane_e;
-  const int frag_row = lane & 15, frag_q = lane >> 4;
+  const int lane = lane_id_here();
+  const int frag_row = opaque_sign(lane & 15), frag_q = lane >> 4;
   const long long n0 = bn0 + wcol0 + frag_q * 4;                       // + 16 j
   const long long m0 = bm0 + wrow0;                                    // the wave's first row (wave-uniform)
   // sample / position of the wave's first row (GATE_RESID)
@@ -72,7 +85,7 @@ __device__ __forceinline__ void epilogue_w4(const GemmP& p, char* smem, f32x4 (&
       if constexpr (HAS_G) gate[j] = *(const u32x2*)((g_pos < p.split ? p.gate0 : p.gate1) + g_b * p.gate_stride + n0 + 16 * j);
       else gate[j] = u32x2{0u, 0u};
     }
-    const int r4 = lane >> 4, chunk = lane & 15;                        // row layout
+    const int r4 = lane >> 4, chunk = opaque_sign(lane & 15);           // row layout
     const bf16_t* rbase = HAS_R ? p.resid + m0 * p.ldr + n0 : nullptr;  // + row * ldr
     bf16_t* cbase = p.C + (m0 + r4) * p.ldc + (bn0 + wcol0 + chunk * 8);
     char* wput = smem + 131072 + wave * 8192 + frag_row * 256 + (frag_q & 1) * 8;
@@ -94,7 +107,7 @@ __device__ __forceinline__ void epilogue_w4(const GemmP& p, char* smem, f32x4 (&
         while (pos >= p.rows_per_batch) pos -= p.rows_per_batch;
         const int rp = (int)pos - p.rope_text_len;
         if (rp >= 0) qk_video |= 1u << st;
-        const long long ro = (long long)(rp > 0 ? rp : 0) * 64 + (chunk & 7) * 8;
+        const long long ro = (long long)opaque_sign(rp > 0 ? rp : 0) * 64 + opaque_sign(chunk & 7) * 8;
         f32x4(&dst)[4] = qk_tab[st % 3];
         dst[0] = *(const f32x4*)(p.rcos + ro); dst[1] = *(const f32x4*)(p.rcos + ro + 4);
         dst[2] = *(const f32x4*)(p.rsin + ro); dst[3] = *(const f32x4*)(p.rsin + ro + 4);
@@ -208,10 +221,8 @@ __device__ __forceinline__ void epilogue_w4(const GemmP& p, char* smem, f32x4 (&
 // epilogues: both halves rounded to bf16 before the product (nn.Linear's output dtype).  Launched only with whole 128-column wave tiles and 16-byte aligned rows.
 template <int EPI>
 __device__ __forceinline__ void epilogue_w4_geglu(const GemmP& p, char* smem, f32x4 (&acc)[8][8], const long long bm0, const long long bn0, const int wave, const int wrow0,
-                                                  const int wcol0, const int lane_in) {
-  int lane_e = lane_in;                                                // laundered: see epilogue_w4
-  asm volatile("" : "+v"(lane_e));
-  const int lane = lane_e;
+                                                  const int wcol0) {
+  const int lane = lane_id_here();                                     // see epilogue_w4
   const int frag_row = lane & 15, frag_q = lane >> 4;
   const long long m0 = bm0 + wrow0;
   if (m0 >= p.M || bn0 + wcol0 >= p.N) return;                         // a wave tile outside the matrix (N % 128 == 0: a wave's columns are all in or all out)
@@ -223,7 +234,7 @@ __device__ __forceinline__ void epilogue_w4_geglu(const GemmP& p, char* smem, f3
     bv[jj] = p.bias ? *(const u32x2*)(p.bias + n0 + 32 * jj) : u32x2{0u, 0u};
     bg[jj] = p.bias ? *(const u32x2*)(p.bias + n0 + 32 * jj + 16) : u32x2{0u, 0u};
   }
-  const int r8 = lane >> 3, chunk = lane & 7;                          // row layout: 8 rows x 8 chunks per instruction
+  const int r8 = lane >> 3, chunk = opaque_sign(lane & 7);             // row layout: 8 rows x 8 chunks per instruction
   bf16_t* cbase = p.C + (m0 + r8) * p.ldc + ((bn0 + wcol0) >> 1) + chunk * 8;
   char* wput = smem + 131072 + wave * 8192 + frag_row * 128 + (frag_q & 1) * 8;
   const char* wget = smem + 131072 + wave * 8192 + r8 * 128 + ((chunk ^ r8) * 16);   // rows r8 and r8 + 8 share (row & 7)
@@ -284,7 +295,8 @@ __device__ __forceinline__ void tile_coords(const GemmP& p, const int L, int& ti
 //   barriers, two counted waits.  Every statement of the K loop is volatile inline asm: hipcc only allocates registers.  (Round-3 attempts with 8-MFMA
 //   blocks and bursts of reads / pieces lost 3-15 % to the 8-wave loop: one wave per SIMD has no partner to hide a burst behind.)
 // * The DMA cursor runs two K-tiles ahead of the MFMAs and simply walks into the workgroup's NEXT tile: when a tile's last MFMA retires, the first two
-//   K-tiles of the next one are in LDS and its first fragments in registers, so the matrix pipe idles only for the epilogue's own instructions -- not for
+//   K-tiles of the next one are in LDS (its first fragments are read again behind the epilogue: one LDS latency, and 64 registers the epilogue does not have to
+//   spill around), so the matrix pipe idles only for the epilogue's own instructions -- not for
 //   a workgroup launch, an address set-up and a cold first fetch per tile (measured on the non-persistent form of this loop: 17 us per tile, 18 % of a
 //   K = 3072 tile).  vmcnt is ONE in-order counter for loads and stores: the epilogue first waits for the (old) DMA pieces, then stores, and the first K-tile
 //   behind it runs the variant without a counted wait, so no wait in the loop ever stands behind a store that has just been issued.
@@ -299,8 +311,8 @@ template <int EPI, bool WB = false>
 __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr unsigned STAGE = 65536, WOFF = 32768;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1;
-  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+  const int lane = threadIdx.x & 63;
+  const int wave_s = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), wm = wave_s >> 1, wn = wave_s & 1;   // scalars: the epilogue's row / column origins and branches stay off the VGPRs
   const int tiles = p.tile_limit, nk = (int)(p.K / 64), G = (int)gridDim.x;
   // origin of logical tile (tm, tn): first row, one past the last row that exists for it, element offset of its weight matrix
   auto tile_origin = [&](const int tm, long long& bm0, long long& m_end, long long& w_off) __attribute__((always_inline)) {
@@ -329,8 +341,7 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmP p) {
     long long bm0, m_end, w_off;
     tile_origin(tm, bm0, m_end, w_off);
     const long long bn0 = (long long)tn * 256;
-    int lane_c = lane;                      // laundered (see epilogue_w4): nothing lane-derived of this block may stay live across the K loop
-    asm volatile("" : "+v"(lane_c));
+    const int lane_c = lane_id_here();      // (see epilogue_w4: nothing lane-derived of this block may stay live across the K loop)
     const int prow = lane_c >> 3, pchk = (lane_c & 7) ^ prow;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -415,13 +426,17 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmP p) {
   static_for<16>([&](auto I) __attribute__((always_inline)) { dma(I); });
   advance();
   asm volatile("s_waitcnt vmcnt(16)\n\ts_barrier" ::: "memory");
-  aw0 = rowW + c0; aa0 = rowA + c0;
-  static_for<8>([&](auto J) __attribute__((always_inline)) { constexpr int j = decltype(J)::value; (void)&w0; (void)&aw0; MRAG_W4_RD(w0[j], aw0, j * 2048); });
-  static_for<8>([&](auto J) __attribute__((always_inline)) { constexpr int j = decltype(J)::value; (void)&a0; (void)&aa0; MRAG_W4_RD(a0[j], aa0, j * 2048); });
   unsigned g = 0;
   for (int r = 0;; ++r) {
     const int L = r * G + slot;
     if (L >= tiles) break;
+    // the tile's first fragments (K-tile g, k-step 0), read HERE for every tile and not carried over from the previous tile's last K-tile: that K-tile
+    // issues the same reads (one loop body), but their 64 registers are dead across the epilogue, which would otherwise spill accumulator copies around them
+    // (the reloads stood behind the tile's own stores in the in-order vmcnt).  The stage was published by the barrier in front of that K-tile's k-step 1 (by
+    // the one above for the stream's first tile) and the DMA in flight goes to the other stage; kstep begins with lgkmcnt(0).
+    aw0 = rowW + ((g & 1) ? STAGE : 0u) + c0; aa0 = rowA + ((g & 1) ? STAGE : 0u) + c0;
+    static_for<8>([&](auto J) __attribute__((always_inline)) { constexpr int j = decltype(J)::value; (void)&w0; (void)&aw0; MRAG_W4_RD(w0[j], aw0, j * 2048); });
+    static_for<8>([&](auto J) __attribute__((always_inline)) { constexpr int j = decltype(J)::value; (void)&a0; (void)&aa0; MRAG_W4_RD(a0[j], aa0, j * 2048); });
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -433,13 +448,14 @@ __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmP p) {
     }
     // the MFMAs above are invisible to hipcc's hazard pass: the accumulators are read (v_accvgpr_read) only after the matrix pipe has drained; every DMA piece
     // in flight (issued BEFORE the stores below) is waited for here, so the next counted wait in the loop comes two K-tiles after the stores
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15\n\ts_nop 15\n\ts_nop 7" ::: "memory");
+    // (lgkmcnt(0): the last K-tile's k-step-1 reads have landed before hipcc reuses their -- now dead -- registers in the epilogue)
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15\n\ts_nop 7" ::: "memory");
     int tm, tn;
     tile_coords(p, L, tm, tn);
     long long e_bm0, e_mend, e_woff;
     tile_origin(tm, e_bm0, e_mend, e_woff);
-    if constexpr (is_geglu<EPI>) epilogue_w4_geglu<EPI>(p, smem, acc, e_bm0, (long long)tn * 256, wave, wm * 128, wn * 128, lane);
-    else epilogue_w4<EPI>(p, smem, acc, e_bm0, (long long)tn * 256, wave, wm * 128, wn * 128, lane, e_mend);
+    if constexpr (is_geglu<EPI>) epilogue_w4_geglu<EPI>(p, smem, acc, e_bm0, (long long)tn * 256, wave_s, wm * 128, wn * 128);
+    else epilogue_w4<EPI>(p, smem, acc, e_bm0, (long long)tn * 256, wave_s, wm * 128, wn * 128, e_mend);
   }
 #undef MRAG_W4_MF
 #undef MRAG_W4_RD
