@@ -270,6 +270,39 @@ int mrag_gemm_fp8_k64(void* stream, const mrag_gemm_fp8_args* args);
  * launches, slot 1 mrag_layernorm_e4m3 launches (not its MRAG_ENOTSUP returns).  Copies min(n, 2) slots into out_host (HOST memory), returns 2. */
 int mrag_gemm_fp8_k64_launch_counts(uint64_t* out_host, int32_t n);
 
+/* The 320-channel feed-forward of the UNets' transformer blocks in ONE launch -- OPT-IN (layers.set_ff_fusion).  Stands behind FeedForward / GEGLU
+ * (DynamiCrafter lvdm/modules/attention.py:448-475, diffusers FeedForward) together with the pre-norm and the residual of its call site,
+ * `x = self.ff(self.norm3(x)) + x` in BasicTransformerBlock._forward (lvdm/modules/attention.py:265):
+ *   out = x + W2 . ( value * gelu_erf(gate) ) + b2,   [value | gate] = W1 . LayerNorm(x) + b1          (dropout is the identity)
+ * for x [rows, 320] bf16.  Rounding points: the LayerNorm (statistics and affine in fp32) is rounded to bf16; value * gelu_erf(gate), on the fp32
+ * accumulators plus bias, is rounded to bf16; the second product's fp32 accumulation plus b2 plus x is rounded to bf16 once.  Neither the normalised
+ * rows nor the hidden tensor touch memory.  w1 [2 inner, 320] and b1 [2 inner] arrive in the 16-row [value | gate] interleave of MRAG_EPI_GEGLU
+ * (ops.geglu_interleave), w2 [320, inner] in the nn.Linear layout, both with contiguous rows; ln_gamma, ln_beta, b1 and b2 may each be NULL.
+ * MRAG_ENOTSUP unless C == 320, inner % 64 == 0 and 64 <= inner <= 2^20 (mrag_ff_fused_supported; any rows >= 1).  MRAG_EINVAL for a null x / out / w1 / w2,
+ * a pointer that is not 16-byte aligned, rows <= 0, a row stride below 320 or not a multiple of 8 elements, or out overlapping x (a workgroup reads
+ * its rows of x before it writes any of out, but other workgroups' rows at any time).  Every check returns before any launch.
+ * A workgroup owns MRAG_FF_FUSED_ROWS rows; a row's result does not depend on the call's row count.                                               */
+#define MRAG_FF_FUSED_ROWS 128
+typedef struct mrag_ff_fused_args {
+  const void* x;           /* [rows, 320] bf16, ldx                               */
+  void* out;               /* [rows, 320] bf16, ldo                               */
+  const void* ln_gamma;    /* [320] bf16 or NULL                                  */
+  const void* ln_beta;     /* [320] bf16 or NULL                                  */
+  const void* w1;          /* [2 inner, 320] bf16, interleaved, contiguous        */
+  const void* b1;          /* [2 inner] bf16, interleaved, or NULL                */
+  const void* w2;          /* [320, inner] bf16, contiguous                       */
+  const void* b2;          /* [320] bf16 or NULL                                  */
+  int64_t rows, C, inner;
+  int64_t ldx, ldo;        /* elements */
+  float eps;
+} mrag_ff_fused_args;
+int mrag_ff_fused_bf16(void* stream, const mrag_ff_fused_args* args);
+/* 1 when mrag_ff_fused_bf16 takes the shape, else 0 */
+int mrag_ff_fused_supported(int64_t C, int64_t inner);
+/* host-side relaxed launch counter in the form of mrag_gemm_fp8_k64_launch_counts: ONE slot, the launches of mrag_ff_fused_bf16 (not its refusals).
+ * Copies min(n, 1) slots into out_host (HOST memory), returns 1; answers without a device.  enum mrag_kernel_id keeps its enumerators.           */
+int mrag_ff_fused_launch_counts(uint64_t* out_host, int32_t n);
+
 /* ------------------------------------------------------------------------ */
 /* Attention, head_dim 64, bf16, flash-style (no S x S matrix in HBM).       */
 /*   O[b, sq, h*64+d] = resid + out_scale * softmax(Q K^T * scale [+mask]) V */

@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libmrag_hip.so")
 # compiled in this order, at most MAX_COMPILERS at a time: the long units first, so that none of them starts late behind the short ones
-SOURCES = ["gemm_tiled.hip", "gemm_w4.hip", "topk_scan.hip", "gemm_conv.hip", "attn16.hip", "topk_dense.hip", "topk_mfma.hip", "attn_flash.hip", "gemm_skinny.hip", "gemm_fp8.hip", "conv_fp8.hip", "api.hip", "gemm_bf16.hip", "gemm_k320.hip", "attn_fp8.hip",
+SOURCES = ["gemm_tiled.hip", "gemm_w4.hip", "topk_scan.hip", "gemm_conv.hip", "attn16.hip", "topk_dense.hip", "topk_mfma.hip", "attn_flash.hip", "gemm_skinny.hip", "gemm_fp8.hip", "ff_fused.hip", "conv_fp8.hip", "api.hip", "gemm_bf16.hip", "gemm_k320.hip", "attn_fp8.hip",
            "comm.hip", "norm.hip", "pointwise.hip", "preprocess.hip", "unet_ops.hip", "cama_seq.hip", "attn_small.hip", "topk.hip", "probe.hip"]
 MAX_COMPILERS = 16
 ABI_VERSION = 11
@@ -39,6 +39,7 @@ SYMBOLS = [
     "mrag_quant_rows_e4m3", "mrag_gemm_fp8", "mrag_fp8_launch_counts", "mrag_conv_fp8", "mrag_conv_fp8_launch_counts",
     "mrag_layernorm_e4m3", "mrag_gemm_fp8_k64", "mrag_gemm_fp8_k64_launch_counts",
     "mrag_groupnorm_split_workspace_bytes", "mrag_groupnorm_partial_bf16", "mrag_groupnorm_apply_stats_bf16", "mrag_swap_outer_bf16",
+    "mrag_ff_fused_bf16", "mrag_ff_fused_supported", "mrag_ff_fused_launch_counts",
 ]
 
 
@@ -74,6 +75,13 @@ class GemmFp8Args(Structure):
         ("lda", c_int64), ("ldw", c_int64), ("ldc", c_int64), ("ldr", c_int64),
         ("rows_per_batch", c_int64), ("split", c_int64), ("gate_stride", c_int64),
         ("epilogue", c_int32),
+    ]
+
+
+class FfFusedArgs(Structure):
+    _fields_ = [
+        ("x", c_void_p), ("out", c_void_p), ("ln_gamma", c_void_p), ("ln_beta", c_void_p), ("w1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p),
+        ("rows", c_int64), ("C", c_int64), ("inner", c_int64), ("ldx", c_int64), ("ldo", c_int64), ("eps", c_float),
     ]
 
 
@@ -304,6 +312,9 @@ def lib() -> ctypes.CDLL:
     L.mrag_layernorm_e4m3.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64]
     L.mrag_gemm_fp8_k64.argtypes = [c_void_p, POINTER(GemmFp8Args)]
     L.mrag_gemm_fp8_k64_launch_counts.argtypes = [c_void_p, c_int32]
+    L.mrag_ff_fused_bf16.argtypes = [c_void_p, POINTER(FfFusedArgs)]
+    L.mrag_ff_fused_supported.argtypes = [c_int64, c_int64]
+    L.mrag_ff_fused_launch_counts.argtypes = [c_void_p, c_int32]
     L.mrag_gemm_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
     L.mrag_gemm_workspace_bytes.restype = c_int64
     L.mrag_attn_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]

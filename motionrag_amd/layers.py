@@ -153,13 +153,41 @@ def set_ff_precision(module: nn.Module, precision: str = "bf16", sites=FF_SITES)
     return module
 
 
+FF_FUSION_ATTR = "_mrag_ff_fused"
+# A marked feed-forward takes the fused launch from this many rows on: the smallest row count at which it did not lose to the three launches in the table
+# of tools/ff_fused_measure.py -- 258 048 (SVD's level 0) 1.09x, 294 912 (DynamiCrafter-1024's) 1.11x; 18 432 rows 0.94x, 4 608 rows 0.58x (a
+# workgroup's 128 rows take ~95 us whatever the row count: below a few rounds of 256 workgroups the three launches win).  Tests of reduced models set it to 0.
+FF_FUSED_MIN_ROWS = 258048
+
+
+def set_ff_fusion(module: nn.Module, on: bool = True) -> nn.Module:
+    """marks every dynamicrafter.FeedForward and svd_unet.FeedForward under `module`: a marked one runs LayerNorm, GEGLU projection, output projection and
+    residual as ONE launch (ops.ff_fused, mrag_ff_fused_bf16: the normalised rows and the hidden tensor stay on chip) where `ops.ff_fused_supported` admits
+    it -- 320 channels, the UNets' level 0 -- and the call has at least FF_FUSED_MIN_ROWS rows; everywhere else it runs as before.  bf16 with the rounding
+    points of the three launches.  A module also marked by `set_ff_precision` takes the fused bf16 launch where it applies (C = 320, where FF2-fp8 is off
+    by rule anyway) and its fp8 sites elsewhere.  `on=False` unmarks.  Returns the module."""
+    from . import dynamicrafter, svd_unet
+    if not isinstance(on, bool):
+        raise ValueError(f"set_ff_fusion: on must be a bool, got {on!r}")
+    for m in module.modules():
+        if isinstance(m, (dynamicrafter.FeedForward, svd_unet.FeedForward)):
+            setattr(m, FF_FUSION_ATTR, on)
+    return module
+
+
 def feed_forward(ff: nn.Module, norm: nn.LayerNorm, x: torch.Tensor) -> torch.Tensor:
     """x + ff(norm(x)) of a pre-norm transformer block for a GEGLU FeedForward (`ff.net`: GEGLU, Dropout, Linear).  Unmarked (the default): the
-    LayerNorm launch and `ff` exactly as the block called them before; marked by `set_ff_precision`: the sites that are on run on the e4m3 GEMM."""
+    LayerNorm launch and `ff` exactly as the block called them before; marked by `set_ff_fusion`: one fused launch at 320 channels; marked by
+    `set_ff_precision`: the sites that are on run on the e4m3 GEMM.  Marked for both: the fused bf16 launch where it applies, the fp8 sites elsewhere."""
     pj, out = ff.net[0].proj, ff.net[2]
     sites = getattr(ff, FF_SITES_ATTR, ())
     C, inner = pj.weight.shape[1], out.weight.shape[1]
     rows = x.numel() // C
+    if (getattr(ff, FF_FUSION_ATTR, False) and ops.ff_fused_supported(C, inner) and out.weight.shape[0] == C and rows >= FF_FUSED_MIN_ROWS
+            and rows > 0 and pj.weight.shape[0] == 2 * inner):
+        w, b = CACHE.get(("geglu", id(pj)), (pj.weight, pj.bias), lambda: ops.geglu_interleave(pj.weight, pj.bias))
+        w2 = out.weight if out.weight.is_contiguous() else CACHE.get(("ff2c", id(out)), out.weight, lambda: out.weight.detach().contiguous())
+        return ops.ff_fused(x, norm.weight, norm.bias, norm.eps, w, b, w2, out.bias)
     if sites and (rows < FF_FP8_MIN_ROWS or out.weight.shape[0] != C):
         sites = ()
     ff1 = "ff1" in sites and ops.fp8_linear_k64_supported(2 * inner, C, ops.EPI_GEGLU)

@@ -12,7 +12,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, GemmArgs, GemmFp8Args, LnArgs, QkNormRopeArgs, check
+from ._lib import AttnArgs, FfFusedArgs, GemmArgs, GemmFp8Args, LnArgs, QkNormRopeArgs, check
 
 EPI_NONE, EPI_GELU_TANH, EPI_GELU_ERF, EPI_RESID, EPI_GATE_RESID, EPI_SILU, EPI_GEGLU, EPI_QKNORM_ROPE = range(8)
 LOG2E = 1.4426950408889634
@@ -620,6 +620,71 @@ def linear_fp8_k64(x, w8: torch.Tensor, w_exp: torch.Tensor, bias: Optional[torc
     if r2 is not None and tuple(r2.shape) != (M, N):
         raise ValueError(f"linear_fp8_k64: resid {tuple(resid.shape)} is not [{M}, {N}]")
     _fp8_gemm_launch("mrag_gemm_fp8_k64", a, a8, a_exp, o2, r2)
+    return out
+
+
+FF_FUSED_ROWS = 128          # rows per workgroup of mrag_ff_fused_bf16 (MRAG_FF_FUSED_ROWS); its grid is ceil(rows / FF_FUSED_ROWS), neither persistent nor capped
+FF_FUSED_MAX_INNER = 1 << 20
+
+
+def ff_fused_supported(C: int, inner: int) -> bool:
+    """shapes mrag_ff_fused_bf16 takes (include/mrag_hip.h): C == 320, inner % 64 == 0, 64 <= inner <= 2^20; any row count"""
+    return C == 320 and inner >= 64 and inner % 64 == 0 and inner <= FF_FUSED_MAX_INNER
+
+
+def ff_fused_launches() -> int:
+    """launches of mrag_ff_fused_bf16 so far (mrag_ff_fused_launch_counts; refused calls do not count)"""
+    buf = (ctypes.c_uint64 * 1)()
+    _lib.lib().mrag_ff_fused_launch_counts(buf, 1)
+    return int(buf[0])
+
+
+def ff_fused(x: torch.Tensor, ln_weight: Optional[torch.Tensor], ln_bias: Optional[torch.Tensor], eps: float, w1_interleaved: torch.Tensor,
+             b1_interleaved: Optional[torch.Tensor], w2: torch.Tensor, b2: Optional[torch.Tensor], *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x + W2 (value * gelu_erf(gate)) + b2 with [value | gate] = W1 LayerNorm(x) + b1 in ONE launch (mrag_ff_fused_bf16): x [..., 320] bf16;
+    (w1_interleaved [2 inner, 320], b1_interleaved [2 inner]) = geglu_interleave(proj.weight, proj.bias); w2 [320, inner]; ln_weight, ln_bias, b1 and b2
+    may each be None.  Rounds where the three launches it replaces round (the LayerNorm output, the hidden tensor, the result).  `out`: x's shape,
+    not overlapping x.  Raises on what the kernel does not take (`ff_fused_supported`)."""
+    for name, t in (("x", x), ("ln_weight", ln_weight), ("ln_bias", ln_bias), ("w1", w1_interleaved), ("b1", b1_interleaved), ("w2", w2), ("b2", b2), ("out", out)):
+        if t is None and name not in ("x", "w1", "w2"):
+            continue
+        _dev(t, None, name)
+        if t.dtype != torch.bfloat16:
+            raise ValueError(f"ff_fused: {name} must be bf16, got {t.dtype}")
+    C = x.shape[-1]
+    if w2.dim() != 2 or w1_interleaved.dim() != 2:
+        raise ValueError("ff_fused: w1 [2 inner, 320] and w2 [320, inner] are matrices")
+    inner = w2.shape[1]
+    if not ff_fused_supported(C, inner):
+        raise ValueError(f"ff_fused: C={C}, inner={inner} outside the kernel's shapes (C == 320, inner % 64 == 0, inner >= 64)")
+    if tuple(w1_interleaved.shape) != (2 * inner, C) or tuple(w2.shape) != (C, inner):
+        raise ValueError(f"ff_fused: w1 {tuple(w1_interleaved.shape)} / w2 {tuple(w2.shape)} are not [{2 * inner}, {C}] / [{C}, {inner}]")
+    if not w1_interleaved.is_contiguous() or not w2.is_contiguous():
+        raise ValueError("ff_fused: w1 and w2 must be contiguous")
+    for name, t, n in (("ln_weight", ln_weight, C), ("ln_bias", ln_bias, C), ("b1", b1_interleaved, 2 * inner), ("b2", b2, C)):
+        if t is not None and (tuple(t.shape) != (n,) or not t.is_contiguous()):
+            raise ValueError(f"ff_fused: {name} must be a contiguous [{n}] vector, got {tuple(t.shape)}")
+    if x.numel() == 0:
+        raise ValueError("ff_fused: x has no rows")
+    x2 = _rows(x)
+    if x2.stride(0) % 8 != 0 or x2.stride(0) < C or x2.data_ptr() % 16 != 0:
+        x2 = x2.contiguous()
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    elif out is x or tuple(out.shape) != tuple(x.shape) or out.stride(-1) != 1:
+        raise ValueError("ff_fused: out has x's shape, contiguous rows, and is not x")
+    try:
+        o2 = out.view(-1, C)
+    except RuntimeError as e:
+        raise ValueError(f"ff_fused: out's rows are not evenly strided ({e})") from e
+    a = FfFusedArgs()
+    a.x, a.out, a.ln_gamma, a.ln_beta = _p(x2), _p(o2), _p(ln_weight), _p(ln_bias)
+    a.w1, a.b1, a.w2, a.b2 = _p(w1_interleaved), _p(b1_interleaved), _p(w2), _p(b2)
+    a.rows, a.C, a.inner, a.ldx, a.ldo, a.eps = x2.shape[0], C, inner, x2.stride(0), o2.stride(0), eps
+    rc = _lib.lib().mrag_ff_fused_bf16(_stream(), ctypes.byref(a))
+    if rc == _lib.MRAG_EINVAL:
+        raise ValueError("ff_fused: mrag_ff_fused_bf16 refused the arguments (16-byte aligned rows, row strides of a multiple of 8 elements, out not overlapping x)")
+    check(rc, "mrag_ff_fused_bf16")
     return out
 
 
