@@ -20,7 +20,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .layers import WeightCache
+from .layers import WeightCache, linear_resid
 
 
 def packed_score_layout(heads: int, keys: int):
@@ -308,12 +308,10 @@ class APAdapterAttnProcessor2_0(nn.Module):
                 raise NotImplementedError("block_residual with residual_connection / 4-D input")
             # the reference divides the PROCESSOR's output (:139) and the caller adds its x afterwards: x + out / f.  The division rides in the
             # epilogue's acc_scale -- resid + (1 / f) (o W^T + b) -- and must not touch the block's residual
-            out = ops.linear(o, attn.to_out[0].weight, attn.to_out[0].bias, epilogue=ops.EPI_RESID, resid=block_residual, acc_scale=1.0 / rescale)
+            out = linear_resid(o, attn.to_out[0], block_residual, 1.0 / rescale)
             rescale = 1.0
-        elif attn.residual_connection and input_ndim != 4:
-            out = ops.linear(o, attn.to_out[0].weight, attn.to_out[0].bias, epilogue=ops.EPI_RESID, resid=residual.contiguous())
-        else:
-            out = ops.linear(o, attn.to_out[0].weight, attn.to_out[0].bias)        # :129-131
+        else:                                                                      # :129-131
+            out = linear_resid(o, attn.to_out[0], residual.contiguous() if attn.residual_connection and input_ndim != 4 else None)
         if input_ndim == 4:                                                        # :133-134
             out = out.transpose(-1, -2).reshape(b, c, hh, ww)
             if attn.residual_connection:

@@ -26,37 +26,8 @@ import torch
 from torch import nn
 
 from . import ops
-from .layers import CACHE, cat0, conv3x3, conv_t3, feed_forward, host_scalar, lin_w
-
-
-class TembBank:
-    """SiLU(emb) [N, E] together with EVERY residual block's projection of it.  Each ResBlock applies its own `Linear(emb_channels, C_out)` to the
-    same SiLU(emb) (openaimodel3d.py:222; diffusers `time_emb_proj`): 25-44 GEMMs of 28-32 rows per step, each a 20 us launch on 3-10 workgroups.
-    They do not depend on the activations, so the bank runs them as ONE GEMM against the row-concatenated weights at the start of the step and
-    hands out column slices `[N, C_out]` (row stride = the concatenated width).  Same kernel (128 x 128 tiles), same K order per output
-    element as the separate launches: identical bits."""
-
-    def __init__(self, silu_emb: torch.Tensor, owner: nn.Module, linears):
-        self.silu = silu_emb
-        refs = tuple(t for lin in linears for t in (lin.weight, lin.bias))
-        w, b, offs = CACHE.get(("tembbank", id(owner)), refs, lambda: (
-            torch.cat([lin.weight.detach() for lin in linears], dim=0).contiguous(),
-            torch.cat([(lin.bias.detach() if lin.bias is not None else torch.zeros(lin.out_features, dtype=lin.weight.dtype, device=lin.weight.device))
-                       for lin in linears], dim=0).contiguous(),
-            {id(lin): (o, lin.out_features) for lin, o in zip(linears, np.cumsum([0] + [lin.out_features for lin in linears[:-1]]).tolist())}))
-        self._all = ops.linear(silu_emb, w, b) if linears else None
-        self._offs = offs
-
-    def proj(self, lin: nn.Linear) -> torch.Tensor:
-        ent = self._offs.get(id(lin))
-        if ent is None or ent[0] % 8:                      # a block outside the bank (or an unaligned slice): its own launch
-            return ops.linear(self.silu, lin.weight, lin.bias)
-        return self._all[:, ent[0]:ent[0] + ent[1]]
-
-
-def temb_proj(silu_emb, lin: nn.Linear) -> torch.Tensor:
-    """`lin(SiLU(emb))`: a slice of the step's TembBank, or the plain projection when a block is driven with a bare tensor (unit tests)"""
-    return silu_emb.proj(lin) if isinstance(silu_emb, TembBank) else ops.linear(silu_emb, lin.weight, lin.bias)
+from .layers import GEGLU, FeedForward, TembBank, temb_proj          # noqa: F401  (shared with the SVD UNet; importable from here as before)
+from .layers import conv3x3, conv_t3, feed_forward, groupnorm_rows, host_scalar, kv_proj, lin_w, linear_resid, resnet2d, self_attention, silu_mlp, temb_bank
 
 
 # ------------------------------------------------------------------------------------------------------ frame-parallel sharding (tier 2)
@@ -82,6 +53,20 @@ def _groupnorm_all_ranks(fp, x: torch.Tensor, gn: nn.GroupNorm, rows_total: int,
     [b, 32, 2] partials, then every rank folds them in rank order and normalises its shard (ops.groupnorm_partial / groupnorm_apply_stats)"""
     partials = fp.gather_stats(ops.groupnorm_partial(x, 32))
     return ops.groupnorm_apply_stats(x, partials, rows_total, gn.weight, gn.bias, 32, gn.eps, silu=silu)
+
+
+def _pixel_side(m: nn.Module, x: torch.Tensor, b: int):
+    """x [(b t), hw, C] of a temporal layer -> (xp, t', gn, back): `xp` [(b t'), hw', C] holds every frame of the pixels this rank works on, `gn(y, norm, silu)`
+    is the GroupNorm over (t, h, w) per sample, `back(y)` returns a result to x's layout.  Unsharded: x itself, its t, `groupnorm_rows`, the identity.  Sharded
+    (`set_frame_parallel`): all frames of this rank's hw / world pixels behind one all-to-all transpose, statistics gathered from every rank, the transpose back."""
+    N, hw, C = x.shape
+    t, fp = N // b, _sharding(m)
+    if fp is None:
+        return x, t, lambda y, norm, silu=False: groupnorm_rows(y, norm, silu=silu, frames_per_sample=t), lambda y: y
+    xp = fp.to_pixels(x.view(b, t, hw, C))                                                       # [b, t_all, hw_loc, C]
+    ta, hwl = xp.shape[1], xp.shape[2]
+    gn = lambda y, norm, silu=False: _groupnorm_all_ranks(fp, y.view(b, ta * hwl, y.shape[-1]), norm, ta * hw, silu).view(b * ta, hwl, -1)
+    return xp.view(b * ta, hwl, C), ta, gn, lambda y: fp.to_frames(y.view(b, ta, hwl, C)).view(N, hw, C)
 
 
 # ------------------------------------------------------------------------------------------------------ attention
@@ -130,11 +115,6 @@ class CrossAttention(nn.Module):
             if action_cross_attention_scale_learnable:
                 self.register_parameter("alpha_action", nn.Parameter(torch.tensor(0.0)))
 
-    def _kv(self, key, wk, wv, ctx):
-        w = CACHE.get((key, id(self)), (wk.weight, wv.weight), lambda: cat0([wk.weight, wv.weight]))
-        kv = ops.linear(ctx.contiguous(), w)
-        return kv[..., : self.inner].unflatten(-1, (self.heads, 64)), kv[..., self.inner:].unflatten(-1, (self.heads, 64))
-
     def forward(self, x: torch.Tensor, context: Optional[dict] = None, mask=None, *, resid: Optional[torch.Tensor] = None, kv_div: int = 1,
                 temporal: Optional[tuple] = None) -> torch.Tensor:
         """x [Nb, L, C] rows.  `resid` is added to the projected output (the block's `+ x`).  `context` tensors may have a
@@ -142,66 +122,27 @@ class CrossAttention(nn.Module):
         are ordered (b, t, hw) and attention runs over t for every (b, hw) (TemporalTransformer, attention.py:399-402)."""
         if mask is not None:
             raise NotImplementedError                                               # attention.py:172-173
-        H, inner = self.heads, self.inner
+        H = self.heads
         Nb, L, _ = x.shape
         if context is None:                                                         # spatial / temporal self-attention  :175-183
-            w = CACHE.get(("qkv", id(self)), (self.to_q.weight, self.to_k.weight, self.to_v.weight), lambda: cat0([self.to_q.weight, self.to_k.weight, self.to_v.weight]))
-            qkv = ops.linear(x, w)
-            if temporal is None:
-                q5 = qkv.view(Nb, L, 3, H, 64)
-                # BASELINE config "fp8 MFMA attention path": opt-in per module (set_attention_precision), long spatial sequences only
-                out = ops.attention(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], fp8=self.attention_precision == "fp8" and ops.fp8_attention_supported(L, L))
-            else:
-                b, t, hw = temporal
-                out = torch.empty(Nb, L, inner, dtype=torch.bfloat16, device=x.device)
-                q6 = qkv.view(b, t, hw, 3, H, 64)
-                o4 = out.view(b, t, hw, inner)
-                for i in range(b):                                                  # batch = hw (stride one row), sequence = t
-                    ops.attention(q6[i, :, :, 0].permute(1, 0, 2, 3), q6[i, :, :, 1].permute(1, 0, 2, 3), q6[i, :, :, 2].permute(1, 0, 2, 3),
-                                  out=o4[i].permute(1, 0, 2))
+            # BASELINE config "fp8 MFMA attention path": opt-in per module (set_attention_precision), long spatial sequences only
+            out = self_attention(self, x, H, temporal=temporal, fp8=self.attention_precision == "fp8")
         else:
             q = ops.linear(x, self.to_q.weight).view(Nb, L, H, 64)
-            k, v = self._kv("kv", self.to_k, self.to_v, context["prompt"])
+            k, v = kv_proj(self, "kv", self.to_k, self.to_v, context["prompt"], H)
             out = ops.attention(q, k, v, kv_batch_div=Nb // k.shape[0])             # :189
             if self.image_cross_attention:                                          # :191-204
-                k, v = self._kv("kv_ip", self.to_k_ip, self.to_v_ip, context["image"])
+                k, v = kv_proj(self, "kv_ip", self.to_k_ip, self.to_v_ip, context["image"], H)
                 s = self.image_cross_attention_scale * ((host_scalar(torch.tanh, self.alpha) + 1) if self.image_cross_attention_scale_learnable else 1.0)
                 ops.attention(q, k, v, out=out, resid=out, kv_batch_div=Nb // k.shape[0], out_scale=float(s))
             if self.action_cross_attention:                                         # :206-220  q_a = to_q_a(out)
                 q_a = ops.linear(out, self.to_q_a.weight).view(Nb, L, H, 64)
-                k, v = self._kv("kv_a", self.to_k_a, self.to_v_a, context["action"])
+                k, v = kv_proj(self, "kv_a", self.to_k_a, self.to_v_a, context["action"], H)
                 s = self.action_cross_attention_scale * ((host_scalar(torch.tanh, self.alpha_action) + 1) if self.action_cross_attention_scale_learnable else 1.0)
                 ops.attention(q_a, k, v, out=out, resid=out, kv_batch_div=Nb // k.shape[0], out_scale=float(s))
-        if resid is not None:
-            return ops.linear(out, self.to_out[0].weight, self.to_out[0].bias, epilogue=ops.EPI_RESID, resid=resid)
-        return ops.linear(out, self.to_out[0].weight, self.to_out[0].bias)          # :222-223
+        return linear_resid(out, self.to_out[0], resid)                            # :222-223
 
     efficient_forward = forward
-
-
-class GEGLU(nn.Module):
-    def __init__(self, dim_in, dim_out):
-        super().__init__()
-        self.proj = nn.Linear(dim_in, dim_out * 2)
-
-
-class FeedForward(nn.Module):
-    """attention.py:458-475 with glu=True"""
-
-    def __init__(self, dim, dim_out=None, mult=4, glu=True, dropout=0.0):
-        super().__init__()
-        if not glu:
-            raise NotImplementedError("the UNet uses gated_ff=True")
-        inner = int(dim * mult)
-        self.net = nn.Sequential(GEGLU(dim, inner), nn.Dropout(dropout), nn.Linear(inner, dim if dim_out is None else dim_out))
-
-    def forward(self, x, resid=None):
-        pj = self.net[0].proj
-        w, b = CACHE.get(("geglu", id(pj)), (pj.weight, pj.bias), lambda: ops.geglu_interleave(pj.weight, pj.bias))
-        h = ops.linear(x, w, b, epilogue=ops.EPI_GEGLU)                             # value * gelu(gate) in the GEMM epilogue
-        if resid is not None:
-            return ops.linear(h, self.net[2].weight, self.net[2].bias, epilogue=ops.EPI_RESID, resid=resid)
-        return ops.linear(h, self.net[2].weight, self.net[2].bias)
 
 
 class BasicTransformerBlock(nn.Module):
@@ -253,8 +194,7 @@ class SpatialTransformer(nn.Module):
         """x [(b t), H, W, C]"""
         N, H, W, C = x.shape
         rows = x.view(N, H * W, C)
-        y = ops.groupnorm(rows, self.norm.weight, self.norm.bias, 32, self.norm.eps)
-        y = ops.linear(y, self.proj_in.weight, self.proj_in.bias)
+        y = ops.linear(groupnorm_rows(rows, self.norm), self.proj_in.weight, self.proj_in.bias)
         for blk in self.transformer_blocks:
             y = blk(y, context=context)
         return ops.linear(y, self.proj_out.weight, self.proj_out.bias, epilogue=ops.EPI_RESID, resid=rows).view(N, H, W, C)   # + x_in :332
@@ -286,22 +226,11 @@ class TemporalTransformer(nn.Module):
     def forward(self, x: torch.Tensor, b: int, context=None) -> torch.Tensor:
         """x [(b t), H, W, C]; GroupNorm statistics over (t, h, w) per sample (5-D input in the reference, :397-398)"""
         N, H, W, C = x.shape
-        t, hw = N // b, H * W
-        fp = _sharding(self)
-        if fp is not None:
-            xp = fp.to_pixels(x.view(b, t, hw, C))                                                   # [b, t_all, hw_loc, C]
-            ta, hwl = xp.shape[1], xp.shape[2]
-            y = _groupnorm_all_ranks(fp, xp.view(b, ta * hwl, C), self.norm, ta * hw).view(b * ta, hwl, C)
-            y = ops.linear(y, lin_w(self.proj_in), self.proj_in.bias)
-            for blk in self.transformer_blocks:
-                y = blk(y, context=None, temporal=(b, ta, hwl))
-            y = ops.linear(y, lin_w(self.proj_out), self.proj_out.bias, epilogue=ops.EPI_RESID, resid=xp.view(b * ta, hwl, C))
-            return fp.to_frames(y.view(b, ta, hwl, C)).view(N, H, W, C)
-        y = ops.groupnorm(x.view(b, t * hw, C), self.norm.weight, self.norm.bias, 32, self.norm.eps).view(N, hw, C)
-        y = ops.linear(y, lin_w(self.proj_in), self.proj_in.bias)
+        xp, t, gn, back = _pixel_side(self, x.view(N, H * W, C), b)
+        y = ops.linear(gn(xp, self.norm), lin_w(self.proj_in), self.proj_in.bias)
         for blk in self.transformer_blocks:
-            y = blk(y, context=None, temporal=(b, t, hw))
-        return ops.linear(y, lin_w(self.proj_out), self.proj_out.bias, epilogue=ops.EPI_RESID, resid=x.view(N, hw, C)).view(N, H, W, C)
+            y = blk(y, context=None, temporal=(b, t, xp.shape[1]))
+        return back(ops.linear(y, lin_w(self.proj_out), self.proj_out.bias, epilogue=ops.EPI_RESID, resid=xp)).view(N, H, W, C)
 
 
 # ------------------------------------------------------------------------------------------------------ conv blocks
@@ -322,24 +251,11 @@ class TemporalConvBlock(nn.Module):
 
     def forward(self, x: torch.Tensor, b: int) -> torch.Tensor:
         """x [(b t), HW, C]"""
-        N, HW, C = x.shape
-        t = N // b
-        fp = _sharding(self)
-        if fp is not None:
-            xp = fp.to_pixels(x.view(b, t, HW, C))                                                   # [b, t_all, hw_loc, C]
-            ta, hwl = xp.shape[1], xp.shape[2]
-            xp = xp.view(b * ta, hwl, C)
-            y = xp
-            for i, seq in enumerate((self.conv1, self.conv2, self.conv3, self.conv4)):
-                y = _groupnorm_all_ranks(fp, y.view(b, ta * hwl, y.shape[-1]), seq[0], ta * HW, silu=True).view(b * ta, hwl, -1)
-                y = conv_t3(y, seq[-1], b, ta, resid=xp if i == 3 else None)
-            return fp.to_frames(y.view(b, ta, hwl, C)).view(N, HW, C)
-        y = x
+        xp, t, gn, back = _pixel_side(self, x, b)
+        y = xp
         for i, seq in enumerate((self.conv1, self.conv2, self.conv3, self.conv4)):
-            gn = seq[0]
-            y = ops.groupnorm(y.view(b, t * HW, y.shape[-1]), gn.weight, gn.bias, 32, gn.eps, silu=True).view(N, HW, -1)
-            y = conv_t3(y, seq[-1], b, t, resid=x if i == 3 else None)               # identity + x  :281
-        return y
+            y = conv_t3(gn(y, seq[0], True), seq[-1], b, t, resid=xp if i == 3 else None)       # identity + x  :281
+        return back(y)
 
 
 class ResBlock(nn.Module):
@@ -365,19 +281,10 @@ class ResBlock(nn.Module):
 
     def forward(self, x: torch.Tensor, silu_emb: torch.Tensor, batch_size: Optional[int] = None) -> torch.Tensor:
         """x [(b t), H, W, C]; silu_emb = SiLU(emb) [(b t), emb_channels] (shared by every ResBlock of the step)"""
-        N, H, W, C = x.shape
-        gi, go = self.in_layers[0], self.out_layers[0]
-        h = ops.groupnorm(x.view(N, H * W, C), gi.weight, gi.bias, 32, gi.eps, silu=True).view(N, H, W, C)
-        h = conv3x3(h, self.in_layers[2])
-        emb_out = temb_proj(silu_emb, self.emb_layers[1])                                                      # :222 (one batched GEMM per step: TembBank)
-        h = ops.groupnorm(h.view(N, H * W, -1), go.weight, go.bias, 32, go.eps, silu=True, emb=emb_out).view(N, H, W, -1)   # h + emb_out -> GN -> SiLU
-        if isinstance(self.skip_connection, nn.Identity):
-            skip = x
-        elif self.skip_connection.kernel_size == (1, 1):
-            skip = ops.linear(x, lin_w(self.skip_connection), self.skip_connection.bias)
-        else:
-            skip = conv3x3(x, self.skip_connection)
-        h = conv3x3(h, self.out_layers[3], resid=skip)                                                          # skip + h  :231
+        N, H, W, _ = x.shape
+        # h + emb_layers(emb) -> GN -> SiLU (:222: one batched GEMM per step, TembBank); skip + h in the last convolution's epilogue (:231)
+        h = resnet2d(x, self.in_layers[0], self.in_layers[2], self.out_layers[0], self.out_layers[3], self.skip_connection, temb=silu_emb, temb_lin=self.emb_layers[1],
+                     conv=conv3x3)
         if self.use_temporal_conv and batch_size:
             h = self.temopral_conv(h.view(N, H * W, -1), batch_size).view(N, H, W, -1)
         return h
@@ -504,7 +411,7 @@ class UNetModel(nn.Module):
             fp.check(t, self._level_pixels(hh, ww))
             fr = fp.frames(t)
             x, t = x[:, :, fr.start:fr.stop], len(fr)
-        mlp = lambda seq, e: ops.linear(ops.linear(e, seq[0].weight, seq[0].bias, epilogue=ops.EPI_SILU), seq[2].weight, seq[2].bias)
+        mlp = lambda seq, e: silu_mlp(seq[0], seq[2], e)                        # nn.Sequential(Linear, SiLU, Linear)
         emb = mlp(self.time_embed, ops.timestep_embedding(timesteps.to(dev, torch.float32), self.model_channels))      # :581-582
         ctx = {}
         if "image" in context:
@@ -522,9 +429,7 @@ class UNetModel(nn.Module):
                 fs = torch.tensor([self.default_fs] * b, dtype=torch.long, device=dev)
             emb = ops.add(emb, mlp(self.fps_embedding, ops.timestep_embedding(fs.to(dev, torch.float32), self.model_channels)))
         silu_emb = ops.silu(emb).repeat_interleave(t, dim=0).contiguous()                                               # every ResBlock uses SiLU(emb)
-        if getattr(self, "_temb_linears", None) is None:
-            self._temb_linears = [m.emb_layers[1] for m in self.modules() if isinstance(m, ResBlock)]
-        silu_emb = TembBank(silu_emb, self, self._temb_linears)
+        silu_emb = temb_bank(self, silu_emb, lambda m: m.emb_layers[1] if isinstance(m, ResBlock) else None)
         h = x.to(torch.bfloat16).permute(0, 2, 3, 4, 1).reshape(b * t, hh, ww, c).contiguous()                          # b c t h w -> (b t) h w c
         hs = []
         for i, module in enumerate(self.input_blocks):
@@ -536,10 +441,8 @@ class UNetModel(nn.Module):
         for module in self.output_blocks:
             h = torch.cat([h, hs.pop()], dim=-1)                                                                        # channel concat (memory only)
             h = module(h, silu_emb, context=ctx, batch_size=b)
-        N, H, W, C = h.shape
-        go = self.out[0]
-        y = conv3x3(ops.groupnorm(h.view(N, H * W, C), go.weight, go.bias, 32, go.eps, silu=True).view(N, H, W, C), self.out[2])
-        y = y.view(b, t, H, W, -1)
+        y = conv3x3(groupnorm_rows(h, self.out[0], silu=True), self.out[2])
+        y = y.view(b, t, *y.shape[1:])
         if fp is not None:
             y = fp.gather_frames(y)                                    # [b, t_all, H, W, c_out] on every rank
         return y.permute(0, 4, 1, 2, 3).contiguous()

@@ -12,7 +12,7 @@ Data path (channels-last rows, all frames of a clip in one batch -- 16 x 576 x 1
   3x3 convolutions (+ nearest x2)      -> `mrag_conv_bf16` implicit GEMM, the ResnetBlock's `x + h` in the epilogue; conv_in (3 / 4 channels) through the row gather
   Downsample (pad (0,1,0,1), stride 2) -> the same implicit GEMM with `asym_pad` (taps start at the pixel itself, zero row / column at the bottom / right)
   1x1 convolutions / nin_shortcut      -> `mrag_gemm_bf16`
-  AttnBlock (1 head, head_dim 512)     -> q / k projections, S = q k^T as a GEMM per frame, `mrag_softmax_rows_bf16`, V^T produced directly by a GEMM with swapped
+  AttnBlock (1 head, head_dim 512)     -> q / k projections, S = q k^T as a GEMM per frame, the row-softmax kernel, V^T produced directly by a GEMM with swapped
                                           operands (no transpose pass), O = P V^T^T as a GEMM (+ the value bias: rows of P sum to 1), proj_out with the residual.
 GPU only; no CPU fallback.
 """
@@ -22,18 +22,12 @@ import torch
 from torch import nn
 
 from . import ops
-from .layers import CACHE, _conv_small_cin, bf16, conv3x3, lin_w
+from .layers import CACHE, _conv_small_cin, attention_1head, bf16, conv3x3, groupnorm_rows, resnet2d, wb
 
 
 def Normalize(in_channels: int, num_groups: int = 32) -> nn.GroupNorm:
     """ae_modules.py:16-17"""
     return nn.GroupNorm(num_groups=num_groups, num_channels=in_channels, eps=1e-6, affine=True)
-
-
-def _gn_swish(x: torch.Tensor, gn: nn.GroupNorm, silu: bool = True) -> torch.Tensor:
-    """x [N, H, W, C] -> same; GroupNorm over (H W, C / G) per (n, group) [+ x * sigmoid(x)]"""
-    N, H, W, C = x.shape
-    return ops.groupnorm(x.view(N, H * W, C), bf16(gn.weight), bf16(gn.bias), gn.num_groups, gn.eps, silu=silu).view(N, H, W, C)
 
 
 class ResnetBlock(nn.Module):
@@ -56,14 +50,8 @@ class ResnetBlock(nn.Module):
                 self.nin_shortcut = nn.Conv2d(in_channels, out_channels, 1, 1, 0)
 
     def forward(self, x: torch.Tensor, temb=None) -> torch.Tensor:
-        h = conv3x3(_gn_swish(x, self.norm1), self.conv1)
-        h = _gn_swish(h, self.norm2)
-        if self.in_channels != self.out_channels:
-            if self.use_conv_shortcut:
-                x = conv3x3(x, self.conv_shortcut)
-            else:
-                x = ops.linear(x, bf16(lin_w(self.nin_shortcut)), bf16(self.nin_shortcut.bias))
-        return conv3x3(h, self.conv2, resid=x)                               # x + h in the convolution's epilogue
+        shortcut = None if self.in_channels == self.out_channels else self.conv_shortcut if self.use_conv_shortcut else self.nin_shortcut
+        return resnet2d(x, self.norm1, self.conv1, self.norm2, self.conv2, shortcut, conv=conv3x3)            # x + h in the last convolution's epilogue
 
 
 class AttnBlock(nn.Module):
@@ -79,20 +67,7 @@ class AttnBlock(nn.Module):
         self.proj_out = nn.Conv2d(in_channels, in_channels, 1)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        N, H, W, C = x.shape
-        S = H * W
-        h = _gn_swish(x, self.norm, silu=False).view(N, S, C)
-        q = ops.linear(h, bf16(lin_w(self.q)), bf16(self.q.bias))                                   # [N, S, C]
-        k = ops.linear(h, bf16(lin_w(self.k)), bf16(self.k.bias))
-        wv = bf16(lin_w(self.v))
-        a = torch.empty(N, S, C, dtype=torch.bfloat16, device=x.device)
-        scores = torch.empty(S, S, dtype=torch.bfloat16, device=x.device)                         # one frame at a time: 170 MB at 72 x 128
-        for n in range(N):
-            ops.linear(q[n], k[n], out=scores)                                                    # w_[i, j] = sum_c q[i, c] k[j, c]        (:67)
-            ops.softmax_rows(scores, scale=float(C) ** -0.5, out=scores)                          # * c^-0.5, softmax over j                (:68-69)
-            vt = ops.linear(wv, h[n])                                                             # V^T [C, S] = Wv h^T: no transpose pass
-            ops.linear(scores, vt, bf16(self.v.bias), out=a[n])                                     # sum_j w_[i, j] v[j, c] (+ b_v: rows sum to 1)  (:72-75)
-        return ops.linear(a, bf16(lin_w(self.proj_out)), bf16(self.proj_out.bias), epilogue=ops.EPI_RESID, resid=x.view(N, S, C)).view(N, H, W, C)
+        return attention_1head(x, self.norm, wb(self.q), wb(self.k), wb(self.v), wb(self.proj_out))        # :67-75 per frame, proj_out + x
 
 
 class Upsample(nn.Module):
@@ -173,7 +148,7 @@ class Decoder(nn.Module):
                 h = self.up[i].upsample(h)
         if self.give_pre_end:
             return h
-        h = _gn_swish(h, self.norm_out)
+        h = groupnorm_rows(h, self.norm_out, silu=True)
         conv = self.conv_out                                                  # out_ch = 3: the GEMM wants N % 4 == 0 -> one zero output channel, sliced off
 
         def build():
@@ -242,7 +217,7 @@ class Encoder(nn.Module):
             if i < self.num_resolutions - 1:
                 h = lv.downsample(h)
         h = self.mid.block_2(self.mid.attn_1(self.mid.block_1(h)))
-        return conv3x3(_gn_swish(h, self.norm_out), self.conv_out)
+        return conv3x3(groupnorm_rows(h, self.norm_out, silu=True), self.conv_out)
 
 
 class DiagonalGaussianDistribution:
@@ -286,7 +261,7 @@ class AutoencoderKL(nn.Module):
             raise ops.HipOnly("AutoencoderKL.encode: GPU tensors only")
         xc = x.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()
         h = self.encoder(xc)
-        moments = ops.linear(h, bf16(lin_w(self.quant_conv)), bf16(self.quant_conv.bias))
+        moments = ops.linear(h, *wb(self.quant_conv))
         return DiagonalGaussianDistribution(moments.permute(0, 3, 1, 2))
 
     @torch.no_grad()
@@ -305,7 +280,7 @@ class AutoencoderKL(nn.Module):
         outs = []
         for i in range(0, N, chunk):
             zc = z[i:i + chunk].to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()       # channels-last rows (a few KB per frame)
-            zc = ops.linear(zc, bf16(lin_w(self.post_quant_conv)), bf16(self.post_quant_conv.bias))
+            zc = ops.linear(zc, *wb(self.post_quant_conv))
             outs.append(self.decoder(zc).permute(0, 3, 1, 2))
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 

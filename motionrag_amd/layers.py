@@ -1,7 +1,12 @@
 """What the model files share: the derived-weight cache, the bf16 view of a parameter, the empty state-dict namespace, the 3x3 / (3,1,1)
-convolutions as GEMMs and the pre-LayerNorm transformer block.  Host plumbing only: every launch goes through `ops`."""
+convolutions as GEMMs, the pre-LayerNorm transformer block, and ONE body for every block the UNets and VAEs have in common -- `groupnorm_rows`, the spatial and
+temporal residual blocks (`resnet2d`, `resnet_t3`), the GEGLU `FeedForward` with its opt-in paths, the UNets' attention core (`self_attention`, `kv_proj`,
+`linear_resid`), the VAEs' single-head attention, and the timestep plumbing (`TembBank`, `temb_proj`, `temb_bank`, `silu_mlp`).  The model classes keep their
+constructors (hence their state-dict keys) and hand their sub-modules to these functions.  Host plumbing only: every launch goes through `ops`; this file imports
+no model file."""
 from __future__ import annotations
 
+import itertools
 import weakref
 from typing import Optional
 
@@ -66,6 +71,19 @@ def lin_w(m) -> torch.Tensor:
     return w if w.dim() == 2 else CACHE.get(("w2", id(m)), w, lambda: w.detach().reshape(w.shape[0], w.shape[1]).contiguous())
 
 
+def wb(m):
+    """(weight [out, in], bias) of an nn.Linear or a 1x1 convolution, as bf16"""
+    return bf16(lin_w(m)), bf16(m.bias)
+
+
+def linear_resid(x: torch.Tensor, lin, resid: Optional[torch.Tensor] = None, acc_scale: float = 1.0) -> torch.Tensor:
+    """`lin(x)`, or with `resid`: resid + acc_scale * lin(x) in the GEMM's epilogue.  `lin`: an nn.Linear or a (weight [out, in], bias) pair."""
+    w, b = lin if isinstance(lin, tuple) else (lin.weight, lin.bias)
+    if resid is None:
+        return ops.linear(x, w, b)
+    return ops.linear(x, w, b, epilogue=ops.EPI_RESID, resid=resid, acc_scale=acc_scale)
+
+
 def host_scalar(fn, p: torch.Tensor) -> float:
     """`fn` (torch.tanh, torch.sigmoid) of a learnable scalar gate as a host float, read back ONCE per weight version: a `.item()` per
     call is a host sync per layer and cannot be captured in a HIP graph"""
@@ -115,11 +133,7 @@ def conv3x3(x: torch.Tensor, conv: nn.Conv2d, *, stride: int = 1, upsample: bool
     rows = ops.im2col3x3(x, stride=stride, upsample=upsample)
     Hi, Wi = (2 * H, 2 * W) if upsample else (H, W)
     Ho, Wo = (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
-    if resid is not None:
-        y = ops.linear(rows, wk, conv.bias, epilogue=ops.EPI_RESID, resid=resid.reshape(-1, cout))
-    else:
-        y = ops.linear(rows, wk, conv.bias)
-    return y.view(N, Ho, Wo, cout)
+    return linear_resid(rows, (wk, conv.bias), None if resid is None else resid.reshape(-1, cout)).view(N, Ho, Wo, cout)
 
 
 FF_SITES_ATTR = "_mrag_ff_fp8_sites"
@@ -136,19 +150,18 @@ FF2_FP8_MIN_WIDTH = 1280
 
 
 def set_ff_precision(module: nn.Module, precision: str = "bf16", sites=FF_SITES) -> nn.Module:
-    """precision of the feed-forward linears of the UNets' transformer blocks under `module` (every dynamicrafter.FeedForward and svd_unet.FeedForward):
+    """precision of the feed-forward linears of the UNets' transformer blocks under `module` (every `FeedForward`):
     "bf16" (default, the reference precision) or "fp8" -- the e4m3 GEMM mrag_gemm_fp8_k64 (per-row activation exponents, per-output-channel weight
     exponents, fp32 accumulation) at the `sites` named: "ff1" the GEGLU projection, fed by a LayerNorm that writes e4m3 (ops.layernorm_e4m3), "ff2" the
     output projection with its residual, fed by a row quantiser.  Calls of fewer than FF_FP8_MIN_ROWS rows stay bf16, and so does "ff2" below
     FF2_FP8_MIN_ROWS rows or FF2_FP8_MIN_WIDTH channels: the shapes measured to lose, or smaller than any measured.  Returns the module."""
-    from . import dynamicrafter, svd_unet
     if precision not in ("bf16", "fp8"):
         raise ValueError(f"feed-forward precision must be 'bf16' or 'fp8', got {precision!r}")
     sites = tuple(sites)
     if not sites or any(s not in FF_SITES for s in sites):
         raise ValueError(f"feed-forward sites are a non-empty subset of {FF_SITES}, got {sites!r}")
     for m in module.modules():
-        if isinstance(m, (dynamicrafter.FeedForward, svd_unet.FeedForward)):
+        if isinstance(m, FeedForward):
             setattr(m, FF_SITES_ATTR, tuple(s for s in FF_SITES if s in sites) if precision == "fp8" else ())
     return module
 
@@ -161,24 +174,64 @@ FF_FUSED_MIN_ROWS = 258048
 
 
 def set_ff_fusion(module: nn.Module, on: bool = True) -> nn.Module:
-    """marks every dynamicrafter.FeedForward and svd_unet.FeedForward under `module`: a marked one runs LayerNorm, GEGLU projection, output projection and
+    """marks every `FeedForward` under `module`: a marked one runs LayerNorm, GEGLU projection, output projection and
     residual as ONE launch (ops.ff_fused, mrag_ff_fused_bf16: the normalised rows and the hidden tensor stay on chip) where `ops.ff_fused_supported` admits
     it -- 320 channels, the UNets' level 0 -- and the call has at least FF_FUSED_MIN_ROWS rows; everywhere else it runs as before.  bf16 with the rounding
     points of the three launches.  A module also marked by `set_ff_precision` takes the fused bf16 launch where it applies (C = 320, where FF2-fp8 is off
     by rule anyway) and its fp8 sites elsewhere.  `on=False` unmarks.  Returns the module."""
-    from . import dynamicrafter, svd_unet
     if not isinstance(on, bool):
         raise ValueError(f"set_ff_fusion: on must be a bool, got {on!r}")
     for m in module.modules():
-        if isinstance(m, (dynamicrafter.FeedForward, svd_unet.FeedForward)):
+        if isinstance(m, FeedForward):
             setattr(m, FF_FUSION_ATTR, on)
     return module
 
 
-def feed_forward(ff: nn.Module, norm: nn.LayerNorm, x: torch.Tensor) -> torch.Tensor:
-    """x + ff(norm(x)) of a pre-norm transformer block for a GEGLU FeedForward (`ff.net`: GEGLU, Dropout, Linear).  Unmarked (the default): the
-    LayerNorm launch and `ff` exactly as the block called them before; marked by `set_ff_fusion`: one fused launch at 320 channels; marked by
-    `set_ff_precision`: the sites that are on run on the e4m3 GEMM.  Marked for both: the fused bf16 launch where it applies, the fp8 sites elsewhere."""
+class GEGLU(nn.Module):
+    def __init__(self, dim_in, dim_out):
+        super().__init__()
+        self.proj = nn.Linear(dim_in, dim_out * 2)
+
+
+class FeedForward(nn.Module):
+    """the UNets' gated feed-forward (lvdm attention.py:458-475 with glu=True; diffusers' FeedForward with activation_fn "geglu"): state-dict keys
+    `net.0.proj.{weight,bias}`, `net.2.{weight,bias}`"""
+
+    def __init__(self, dim, dim_out=None, mult=4, glu=True, dropout=0.0):
+        super().__init__()
+        if not glu:
+            raise NotImplementedError("the UNets use gated feed-forwards")
+        inner = int(dim * mult)
+        self.net = nn.Sequential(GEGLU(dim, inner), nn.Dropout(dropout), nn.Linear(inner, dim if dim_out is None else dim_out))
+
+    def forward(self, x, resid=None):
+        return _geglu_ff(self, x, resid)
+
+
+def _geglu_ff(ff: FeedForward, x: torch.Tensor, resid: Optional[torch.Tensor], norm: Optional[nn.LayerNorm] = None, ff1: bool = False, ff2: bool = False) -> torch.Tensor:
+    """[resid +] out(GEGLU([norm](x))): value * gelu(gate) in the first GEMM's epilogue, the residual in the second's.  `ff1` / `ff2`: that GEMM on the e4m3
+    kernel (FF1 fed by a LayerNorm that writes e4m3, FF2 by a row quantiser).  The bf16 form normalises before it looks the weights up, the fp8 forms after:
+    the order their first call has always launched in."""
+    pj, out = ff.net[0].proj, ff.net[2]
+    ln = lambda f: x if norm is None else f(x, norm.weight, norm.bias, norm.eps)
+    a = None if ff1 or ff2 else ln(ops.layernorm)
+    w, b = CACHE.get(("geglu", id(pj)), (pj.weight, pj.bias), lambda: ops.geglu_interleave(pj.weight, pj.bias))
+    if ff1:
+        # the weights quantised once per output channel (FF1: the interleaved rows), the activation by the LayerNorm itself
+        w8, w_exp = CACHE.get(("geglu8", id(pj)), (pj.weight, pj.bias), lambda: ops.quant_rows_e4m3(bf16(w)))
+        h = ops.linear_fp8_k64(ln(ops.layernorm_e4m3), w8, w_exp, b, epilogue=ops.EPI_GEGLU).view(*x.shape[:-1], out.weight.shape[1])
+    else:
+        h = ops.linear(ln(ops.layernorm) if a is None else a, w, b, epilogue=ops.EPI_GEGLU)
+    if ff2:
+        w8, w_exp = CACHE.get(("ff2w8", id(out)), out.weight, lambda: ops.quant_rows_e4m3(bf16(out.weight)))
+        return ops.linear_fp8_k64(h, w8, w_exp, out.bias, epilogue=ops.EPI_RESID, resid=resid)
+    return linear_resid(h, out, resid)
+
+
+def feed_forward(ff: FeedForward, norm: nn.LayerNorm, x: torch.Tensor) -> torch.Tensor:
+    """x + ff(norm(x)) of a pre-norm transformer block.  Unmarked (the default): the LayerNorm launch and the two bf16 GEMMs; marked by `set_ff_fusion`: one
+    fused launch at 320 channels; marked by `set_ff_precision`: the sites that are on run on the e4m3 GEMM.  Marked for both: the fused bf16 launch where it
+    applies, the fp8 sites elsewhere."""
     pj, out = ff.net[0].proj, ff.net[2]
     sites = getattr(ff, FF_SITES_ATTR, ())
     C, inner = pj.weight.shape[1], out.weight.shape[1]
@@ -192,20 +245,7 @@ def feed_forward(ff: nn.Module, norm: nn.LayerNorm, x: torch.Tensor) -> torch.Te
         sites = ()
     ff1 = "ff1" in sites and ops.fp8_linear_k64_supported(2 * inner, C, ops.EPI_GEGLU)
     ff2 = "ff2" in sites and rows >= FF2_FP8_MIN_ROWS and C >= FF2_FP8_MIN_WIDTH and ops.fp8_linear_k64_supported(C, inner, ops.EPI_RESID)
-    if not (ff1 or ff2):
-        return ff(ops.layernorm(x, norm.weight, norm.bias, norm.eps), resid=x)
-    w, b = CACHE.get(("geglu", id(pj)), (pj.weight, pj.bias), lambda: ops.geglu_interleave(pj.weight, pj.bias))
-    if ff1:
-        # the weights quantised once per output channel (FF1: the interleaved rows), the activation by the LayerNorm itself
-        w8, w_exp = CACHE.get(("geglu8", id(pj)), (pj.weight, pj.bias), lambda: ops.quant_rows_e4m3(bf16(w)))
-        h = ops.linear_fp8_k64(ops.layernorm_e4m3(x, norm.weight, norm.bias, norm.eps), w8, w_exp, b, epilogue=ops.EPI_GEGLU)
-        h = h.view(*x.shape[:-1], inner)
-    else:
-        h = ops.linear(ops.layernorm(x, norm.weight, norm.bias, norm.eps), w, b, epilogue=ops.EPI_GEGLU)
-    if ff2:
-        w8, w_exp = CACHE.get(("ff2w8", id(out)), out.weight, lambda: ops.quant_rows_e4m3(bf16(out.weight)))
-        return ops.linear_fp8_k64(h, w8, w_exp, out.bias, epilogue=ops.EPI_RESID, resid=x)
-    return ops.linear(h, out.weight, out.bias, epilogue=ops.EPI_RESID, resid=x)
+    return _geglu_ff(ff, x, x, norm, ff1, ff2)
 
 
 def conv_t3(x: torch.Tensor, conv: nn.Conv3d, B: int, T: int, *, resid: Optional[torch.Tensor] = None, acc_scale: float = 1.0) -> torch.Tensor:
@@ -216,9 +256,7 @@ def conv_t3(x: torch.Tensor, conv: nn.Conv3d, B: int, T: int, *, resid: Optional
     if C % 64 == 0:
         return ops.conv_implicit(x.contiguous(), wk, conv.bias, ops.CONV_T3, frames=T, resid=resid.contiguous() if resid is not None else None, acc_scale=acc_scale)
     rows = ops.unfold_t3(x, B, T)
-    if resid is not None:
-        return ops.linear(rows, wk, conv.bias, epilogue=ops.EPI_RESID, resid=resid.reshape(-1, cout), acc_scale=acc_scale).view(x.shape[0], x.shape[1], cout)
-    return ops.linear(rows, wk, conv.bias).view(x.shape[0], x.shape[1], cout)
+    return linear_resid(rows, (wk, conv.bias), None if resid is None else resid.reshape(-1, cout), acc_scale).view(x.shape[0], x.shape[1], cout)
 
 
 def _conv_small_cin(z: torch.Tensor, conv: nn.Conv2d, tag: str) -> torch.Tensor:
@@ -234,6 +272,121 @@ def _conv_small_cin(z: torch.Tensor, conv: nn.Conv2d, tag: str) -> torch.Tensor:
         return torch.nn.functional.pad(w, (0, kp - 9 * cp)).contiguous()
     wk = CACHE.get((tag, id(conv), cp), conv.weight, build)
     return ops.linear(ops.im2col3x3(z.contiguous()), wk, bf16(conv.bias)).view(N, H, W, -1)
+
+
+def groupnorm_rows(x: torch.Tensor, gn: nn.GroupNorm, *, silu: bool = False, frames_per_sample: int = 1, emb: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """GroupNorm [of x + emb] [+ SiLU] of channels-last x [N, H, W, C] or [N, HW, C], returned in x's shape.  Statistics per image, or per clip over (t, h, w)
+    with `frames_per_sample` = t consecutive frames (the temporal blocks' 5-D GroupNorm: a row-count change)."""
+    f = frames_per_sample
+    return ops.groupnorm(x.view(x.shape[0] // f, -1, x.shape[-1]), bf16(gn.weight), bf16(gn.bias), gn.num_groups, gn.eps, silu=silu, emb=emb).view(x.shape)
+
+
+class TembBank:
+    """SiLU(emb) [N, E] together with EVERY residual block's projection of it.  Each ResBlock applies its own `Linear(emb_channels, C_out)` to the
+    same SiLU(emb) (openaimodel3d.py:222; diffusers `time_emb_proj`): 25-44 GEMMs of 28-32 rows per step, each a 20 us launch on 3-10 workgroups.
+    They do not depend on the activations, so the bank runs them as ONE GEMM against the row-concatenated weights at the start of the step and
+    hands out column slices `[N, C_out]` (row stride = the concatenated width).  Same kernel (128 x 128 tiles), same K order per output
+    element as the separate launches: identical bits."""
+
+    def __init__(self, silu_emb: torch.Tensor, owner: nn.Module, linears):
+        self.silu = silu_emb
+        refs = tuple(t for lin in linears for t in (lin.weight, lin.bias))
+        w, b, offs = CACHE.get(("tembbank", id(owner)), refs, lambda: (
+            torch.cat([lin.weight.detach() for lin in linears], dim=0).contiguous(),
+            torch.cat([(lin.bias.detach() if lin.bias is not None else torch.zeros(lin.out_features, dtype=lin.weight.dtype, device=lin.weight.device))
+                       for lin in linears], dim=0).contiguous(),
+            {id(lin): (o, lin.out_features) for lin, o in zip(linears, itertools.accumulate([0] + [lin.out_features for lin in linears[:-1]]))}))
+        self._all = ops.linear(silu_emb, w, b) if linears else None
+        self._offs = offs
+
+    def proj(self, lin: nn.Linear) -> torch.Tensor:
+        ent = self._offs.get(id(lin))
+        if ent is None or ent[0] % 8:                      # a block outside the bank (or an unaligned slice): its own launch
+            return ops.linear(self.silu, lin.weight, lin.bias)
+        return self._all[:, ent[0]:ent[0] + ent[1]]
+
+
+def temb_bank(model: nn.Module, silu_emb: torch.Tensor, pick) -> TembBank:
+    """the step's TembBank over every time-embedding projection of `model`: `pick(module)` returns a residual block's nn.Linear, None for any other module
+    (listed once per model)"""
+    if getattr(model, "_temb_linears", None) is None:
+        model._temb_linears = [lin for lin in map(pick, model.modules()) if lin is not None]
+    return TembBank(silu_emb, model, model._temb_linears)
+
+
+def temb_proj(silu_emb, lin: nn.Linear) -> torch.Tensor:
+    """`lin(SiLU(emb))`: a slice of the step's TembBank, or the plain projection when a block is driven with a bare tensor (unit tests)"""
+    return silu_emb.proj(lin) if isinstance(silu_emb, TembBank) else ops.linear(silu_emb, lin.weight, lin.bias)
+
+
+def silu_mlp(lin1: nn.Linear, lin2: nn.Linear, x: torch.Tensor) -> torch.Tensor:
+    """lin2(SiLU(lin1(x))): the timestep / frame-rate / added-condition embedding MLPs"""
+    return ops.linear(ops.linear(x, lin1.weight, lin1.bias, epilogue=ops.EPI_SILU), lin2.weight, lin2.bias)
+
+
+def resnet2d(x: torch.Tensor, norm1, conv1, norm2, conv2, shortcut=None, *, temb=None, temb_lin: Optional[nn.Linear] = None, conv=None) -> torch.Tensor:
+    """the spatial residual block of both UNets and both VAEs on x [N, H, W, C]: GroupNorm + SiLU, 3x3 convolution, GroupNorm + SiLU [of h + temb_lin(temb)],
+    3x3 convolution with the shortcut as its residual.  `shortcut`: None or nn.Identity, a 1x1 convolution (a GEMM) or a 3x3 one.  `temb`: the step's TembBank or
+    a bare SiLU(emb) [N, E]; its projection is taken between the first convolution and the second norm, where a block driven with a bare tensor launches it.
+    `conv`: the 3x3 convolution; a model file passes its own module-level `conv3x3`, the name tests and measuring tools replace to log or emulate its convolutions."""
+    conv = conv or conv3x3
+    h = conv(groupnorm_rows(x, norm1, silu=True), conv1)
+    h = groupnorm_rows(h, norm2, silu=True, emb=None if temb_lin is None else temb_proj(temb, temb_lin))
+    if shortcut is not None and not isinstance(shortcut, nn.Identity):
+        x = ops.linear(x, *wb(shortcut)) if tuple(shortcut.kernel_size) == (1, 1) else conv(x, shortcut)
+    return conv(h, conv2, resid=x)
+
+
+def resnet_t3(x: torch.Tensor, norm1, conv1, norm2, conv2, b: int, frames: int, *, temb=None, temb_lin: Optional[nn.Linear] = None, acc_scale: float = 1.0) -> torch.Tensor:
+    """the temporal residual block of the SVD UNet and VAE on x [(b f), HW, C]: x + acc_scale * branch(x) with GroupNorm statistics over (f, h, w) per sample and
+    (3, 1, 1) convolutions; `temb_lin(temb)` [(b f), C] is added per frame in front of the second norm"""
+    h = conv_t3(groupnorm_rows(x, norm1, silu=True, frames_per_sample=frames), conv1, b, frames)
+    if temb_lin is not None:
+        h = ops.add_bcast(h, temb_proj(temb, temb_lin), x.shape[1])
+    h = groupnorm_rows(h, norm2, silu=True, frames_per_sample=frames)
+    return conv_t3(h, conv2, b, frames, resid=x, acc_scale=acc_scale)
+
+
+def self_attention(owner: nn.Module, x: torch.Tensor, heads: int, *, temporal: Optional[tuple] = None, fp8: bool = False) -> torch.Tensor:
+    """head_dim-64 self-attention of x [Nb, L, C] through ONE GEMM against the owner's fused `to_q | to_k | to_v`; the result [Nb, L, heads * 64] goes to the
+    owner's output projection.  `temporal=(b, t, hw)`: the rows are ordered (b, t, hw) and attention runs over t for every (b, hw), on permuted views of the
+    projection (no copy).  `fp8`: long spatial sequences (ops.fp8_attention_supported) on the e4m3 MFMA path."""
+    Nb, L, _ = x.shape
+    w = CACHE.get(("qkv", id(owner)), (owner.to_q.weight, owner.to_k.weight, owner.to_v.weight), lambda: cat0([owner.to_q.weight, owner.to_k.weight, owner.to_v.weight]))
+    qkv = ops.linear(x, w)
+    if temporal is None:
+        q5 = qkv.view(Nb, L, 3, heads, 64)
+        return ops.attention(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], fp8=fp8 and ops.fp8_attention_supported(L, L))
+    b, t, hw = temporal
+    out = torch.empty(Nb, L, heads * 64, dtype=torch.bfloat16, device=x.device)
+    q6, o4 = qkv.view(b, t, hw, 3, heads, 64), out.view(b, t, hw, heads * 64)
+    for i in range(b):                                                      # batch = hw (stride one row), sequence = t
+        ops.attention(q6[i, :, :, 0].permute(1, 0, 2, 3), q6[i, :, :, 1].permute(1, 0, 2, 3), q6[i, :, :, 2].permute(1, 0, 2, 3), out=o4[i].permute(1, 0, 2))
+    return out
+
+
+def kv_proj(owner: nn.Module, key: str, to_k: nn.Linear, to_v: nn.Linear, ctx: torch.Tensor, heads: int):
+    """keys and values [B, L, heads, 64] of a cross-attention context through ONE GEMM against the fused `to_k | to_v` (cached under (key, id(owner)))"""
+    w = CACHE.get((key, id(owner)), (to_k.weight, to_v.weight), lambda: cat0([to_k.weight, to_v.weight]))
+    kv = ops.linear(ctx.contiguous(), w)
+    return kv[..., : heads * 64].unflatten(-1, (heads, 64)), kv[..., heads * 64:].unflatten(-1, (heads, 64))
+
+
+def attention_1head(x: torch.Tensor, norm: nn.GroupNorm, q, k, v, out) -> torch.Tensor:
+    """the VAEs' attention block on x [N, H, W, C]: GroupNorm, ONE head over all pixels of a frame with head_dim = C (512), output projection with the residual.
+    `q`, `k`, `v`, `out`: (weight [C, C], bias) pairs.  Per frame: S = q k^T as a GEMM, a row softmax, V^T [C, S] = Wv h^T by a GEMM with swapped operands (no
+    transpose pass), O = P V as a GEMM whose bias is the value bias (rows of P sum to 1).  One [S, S] score buffer: 170 MB at 72 x 128."""
+    N, H, W, C = x.shape
+    S = H * W
+    h = groupnorm_rows(x, norm).view(N, S, C)
+    qs, ks = ops.linear(h, *q), ops.linear(h, *k)
+    a = torch.empty(N, S, C, dtype=torch.bfloat16, device=x.device)
+    scores = torch.empty(S, S, dtype=torch.bfloat16, device=x.device)
+    for n in range(N):
+        ops.linear(qs[n], ks[n], out=scores)
+        ops.softmax_rows(scores, scale=float(C) ** -0.5, out=scores)
+        ops.linear(scores, ops.linear(v[0], h[n]), v[1], out=a[n])
+    return linear_resid(a, out, x.view(N, S, C)).view(N, H, W, C)
 
 
 def prenorm_block(x: torch.Tensor, heads: int, ln1: nn.LayerNorm, qkv_w: torch.Tensor, qkv_b: Optional[torch.Tensor], out_proj: nn.Linear, ln2: nn.LayerNorm,

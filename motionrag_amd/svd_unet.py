@@ -22,8 +22,8 @@ from torch import nn
 
 from . import ops
 from .attn_processor import Attention
-from .dynamicrafter import TembBank, temb_proj
-from .layers import CACHE, cat0, conv3x3, conv_t3, feed_forward, host_scalar
+from .layers import GEGLU, FeedForward          # noqa: F401  (shared with the DynamiCrafter UNet; importable from here as before)
+from .layers import conv3x3, feed_forward, groupnorm_rows, host_scalar, kv_proj, linear_resid, resnet2d, resnet_t3, self_attention, silu_mlp, temb_bank
 
 
 def _ln(n: nn.LayerNorm, x):
@@ -37,7 +37,7 @@ class TimestepEmbedding(nn.Module):
         self.linear_2 = nn.Linear(time_embed_dim, time_embed_dim if out_dim is None else out_dim)
 
     def forward(self, x):
-        return ops.linear(ops.linear(x, self.linear_1.weight, self.linear_1.bias, epilogue=ops.EPI_SILU), self.linear_2.weight, self.linear_2.bias)
+        return silu_mlp(self.linear_1, self.linear_2, x)
 
 
 class AlphaBlender(nn.Module):
@@ -64,16 +64,7 @@ class ResnetBlock2D(nn.Module):
 
     def forward(self, x, silu_temb):
         """x [N, H, W, C]; silu_temb [N, temb] (SiLU already applied)"""
-        N, H, W, C = x.shape
-        h = ops.groupnorm(x.view(N, H * W, C), self.norm1.weight, self.norm1.bias, 32, self.norm1.eps, silu=True).view(N, H, W, C)
-        h = conv3x3(h, self.conv1)
-        t = temb_proj(silu_temb, self.time_emb_proj)                               # a slice of the step's one batched projection (TembBank)
-        co = h.shape[-1]
-        h = ops.groupnorm(h.view(N, H * W, co), self.norm2.weight, self.norm2.bias, 32, self.norm2.eps, silu=True, emb=t).view(N, H, W, co)
-        if self.conv_shortcut is not None:
-            w = CACHE.get(("sc", id(self.conv_shortcut)), self.conv_shortcut.weight, lambda: self.conv_shortcut.weight.detach().reshape(co, C).contiguous())
-            x = ops.linear(x, w, self.conv_shortcut.bias)
-        return conv3x3(h, self.conv2, resid=x)
+        return resnet2d(x, self.norm1, self.conv1, self.norm2, self.conv2, self.conv_shortcut, temb=silu_temb, temb_lin=self.time_emb_proj, conv=conv3x3)
 
 
 class TemporalResnetBlock(nn.Module):
@@ -90,14 +81,7 @@ class TemporalResnetBlock(nn.Module):
     def forward(self, x, silu_temb, b: int, branch_scale: float = 1.0):
         """x [(b f), HW, C]; GroupNorm statistics over (f, h, w) per sample (5-D input in the package).  Returns x + branch_scale * branch(x):
         the block's own `x + h` for 1, the AlphaBlender mix behind it (SpatioTemporalResBlock) for 1 - alpha"""
-        N, HW, C = x.shape
-        f = N // b
-        h = ops.groupnorm(x.view(b, f * HW, C), self.norm1.weight, self.norm1.bias, 32, self.norm1.eps, silu=True).view(N, HW, C)
-        h = conv_t3(h, self.conv1, b, f)
-        t = temb_proj(silu_temb, self.time_emb_proj)                                             # [(b f), C] -> one vector per frame
-        h = ops.add_bcast(h, t, HW)
-        h = ops.groupnorm(h.view(b, f * HW, C), self.norm2.weight, self.norm2.bias, 32, self.norm2.eps, silu=True).view(N, HW, C)
-        return conv_t3(h, self.conv2, b, f, resid=x, acc_scale=branch_scale)
+        return resnet_t3(x, self.norm1, self.conv1, self.norm2, self.conv2, b, x.shape[0] // b, temb=silu_temb, temb_lin=self.time_emb_proj, acc_scale=branch_scale)
 
 
 class SpatioTemporalResBlock(nn.Module):
@@ -126,52 +110,16 @@ class AttnProcessor2_0:
         self.precision = precision
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, temporal=None, block_residual=None, **_):
-        residual = block_residual                                                       # the block's `x` of `x = attn(norm(x)) + x` (not a diffusers argument)
-        x = hidden_states
-        Nb, L, C = x.shape
-        H = attn.heads
+        """`block_residual` (not a diffusers argument): the block's `x` of `x = attn(norm(x)) + x`"""
+        x, H = hidden_states, attn.heads
+        Nb, L, _ = x.shape
         if encoder_hidden_states is None:
-            w = CACHE.get(("qkv", id(attn)), (attn.to_q.weight, attn.to_k.weight, attn.to_v.weight), lambda: cat0([attn.to_q.weight, attn.to_k.weight, attn.to_v.weight]))
-            qkv = ops.linear(x, w)
-            if temporal is None:
-                q5 = qkv.view(Nb, L, 3, H, 64)
-                o = ops.attention(q5[:, :, 0], q5[:, :, 1], q5[:, :, 2], fp8=self.precision == "fp8" and ops.fp8_attention_supported(L, L))
-            else:
-                b, f, hw = temporal
-                o = torch.empty(Nb, L, C, dtype=torch.bfloat16, device=x.device)
-                q6, o4 = qkv.view(b, f, hw, 3, H, 64), o.view(b, f, hw, C)
-                for i in range(b):
-                    ops.attention(q6[i, :, :, 0].permute(1, 0, 2, 3), q6[i, :, :, 1].permute(1, 0, 2, 3), q6[i, :, :, 2].permute(1, 0, 2, 3),
-                                  out=o4[i].permute(1, 0, 2))
+            o = self_attention(attn, x, H, temporal=temporal, fp8=self.precision == "fp8")
         else:
-            ctx = encoder_hidden_states.contiguous()
             q = ops.linear(x, attn.to_q.weight).view(Nb, L, H, 64)
-            wkv = CACHE.get(("kv", id(attn)), (attn.to_k.weight, attn.to_v.weight), lambda: cat0([attn.to_k.weight, attn.to_v.weight]))
-            kv = ops.linear(ctx, wkv)
-            o = ops.attention(q, kv[..., :C].unflatten(-1, (H, 64)), kv[..., C:].unflatten(-1, (H, 64)), kv_batch_div=Nb // ctx.shape[0])
-        if residual is not None:                                                        # block's `attn(norm(x)) + x` in the projection's epilogue
-            return ops.linear(o, attn.to_out[0].weight, attn.to_out[0].bias, epilogue=ops.EPI_RESID, resid=residual)
-        return ops.linear(o, attn.to_out[0].weight, attn.to_out[0].bias)
-
-
-class GEGLU(nn.Module):
-    def __init__(self, dim_in, dim_out):
-        super().__init__()
-        self.proj = nn.Linear(dim_in, dim_out * 2)
-
-
-class FeedForward(nn.Module):
-    def __init__(self, dim, dim_out=None, mult=4):
-        super().__init__()
-        self.net = nn.ModuleList([GEGLU(dim, dim * mult), nn.Dropout(0.0), nn.Linear(dim * mult, dim if dim_out is None else dim_out)])
-
-    def forward(self, x, resid=None):
-        pj = self.net[0].proj
-        w, b = CACHE.get(("geglu", id(pj)), (pj.weight, pj.bias), lambda: ops.geglu_interleave(pj.weight, pj.bias))
-        h = ops.linear(x, w, b, epilogue=ops.EPI_GEGLU)                             # value * gelu(gate) in the GEMM epilogue
-        if resid is not None:
-            return ops.linear(h, self.net[2].weight, self.net[2].bias, epilogue=ops.EPI_RESID, resid=resid)
-        return ops.linear(h, self.net[2].weight, self.net[2].bias)
+            k, v = kv_proj(attn, "kv", attn.to_k, attn.to_v, encoder_hidden_states, H)
+            o = ops.attention(q, k, v, kv_batch_div=Nb // k.shape[0])
+        return linear_resid(o, attn.to_out[0], block_residual)                          # block's `attn(norm(x)) + x` in the projection's epilogue
 
 
 def _attn(dim, heads, head_dim, cross=None):
@@ -266,8 +214,7 @@ class TransformerSpatioTemporalModel(nn.Module):
         image_ctx = encoder_hidden_states[:]                                       # TupleTensor.__getitem__ -> first member (pipeline.py:42-43)
         first = image_ctx.view(b, f, -1, image_ctx.shape[-1])[:, 0]
         rows = x.view(N, hw, C)
-        h = ops.groupnorm(rows, self.norm.weight, self.norm.bias, 32, self.norm.eps)
-        h = ops.linear(h, self.proj_in.weight, self.proj_in.bias)
+        h = ops.linear(groupnorm_rows(rows, self.norm), self.proj_in.weight, self.proj_in.bias)
         idx = torch.arange(f, device=x.device, dtype=torch.float32).repeat(b)
         emb = self.time_pos_embed(ops.timestep_embedding(idx, self.in_channels))   # [(b f), C]
         for blk, tblk in zip(self.transformer_blocks, self.temporal_transformer_blocks):
@@ -420,9 +367,7 @@ class UNetSpatioTemporalConditionModel(nn.Module):
         aug = self.add_embedding(ops.timestep_embedding(tid, self.addition_time_embed_dim).view(B, -1))
         emb = ops.add(emb, aug)
         silu_temb = ops.silu(emb).repeat_interleave(Fr, dim=0)                      # every resnet starts from SiLU(temb)
-        if getattr(self, "_temb_linears", None) is None:
-            self._temb_linears = [m.time_emb_proj for m in self.modules() if isinstance(m, (ResnetBlock2D, TemporalResnetBlock))]
-        silu_temb = TembBank(silu_temb.contiguous(), self, self._temb_linears)
+        silu_temb = temb_bank(self, silu_temb.contiguous(), lambda m: m.time_emb_proj if isinstance(m, (ResnetBlock2D, TemporalResnetBlock)) else None)
         ehs = encoder_hidden_states.repeat_interleave(Fr, dim=0)                    # TupleTensor forwards this to both members (pipeline.py:39-40)
         ehs = ehs.to(torch.bfloat16)
         x = sample.to(torch.bfloat16).permute(0, 1, 3, 4, 2).reshape(B * Fr, H, W, C).contiguous()
@@ -434,10 +379,8 @@ class UNetSpatioTemporalConditionModel(nn.Module):
         x = self.mid_block(x, silu_temb, ehs, B)
         for blk in self.up_blocks:
             x = blk(x, skips, silu_temb, ehs, B)
-        N, Hh, Ww, Cc = x.shape
-        x = ops.groupnorm(x.view(N, Hh * Ww, Cc), self.conv_norm_out.weight, self.conv_norm_out.bias, 32, self.conv_norm_out.eps, silu=True).view(N, Hh, Ww, Cc)
-        x = conv3x3(x, self.conv_out)
-        out = x.view(B, Fr, Hh, Ww, -1).permute(0, 1, 4, 2, 3).contiguous()
+        x = conv3x3(groupnorm_rows(x, self.conv_norm_out, silu=True), self.conv_out)
+        out = x.view(B, Fr, *x.shape[1:]).permute(0, 1, 4, 2, 3).contiguous()
         return UNetOutput(out) if return_dict else (out,)
 
 

@@ -13,14 +13,7 @@ from torch import nn
 
 from . import ops
 from .dynamicrafter_vae import DiagonalGaussianDistribution
-from .layers import CACHE, _conv_small_cin, bf16, conv3x3, conv_t3, host_scalar, lin_w
-
-
-def _gn(x: torch.Tensor, gn: nn.GroupNorm, silu: bool, frames_per_sample: int = 1) -> torch.Tensor:
-    """x [N, H, W, C]; statistics per image, or per clip over (t, h, w) when frames_per_sample > 1 (the temporal blocks' 5-D GroupNorm)"""
-    N, H, W, C = x.shape
-    f = frames_per_sample
-    return ops.groupnorm(x.view(N // f, f * H * W, C), bf16(gn.weight), bf16(gn.bias), gn.num_groups, gn.eps, silu=silu).view(N, H, W, C)
+from .layers import CACHE, _conv_small_cin, attention_1head, bf16, conv3x3, groupnorm_rows, host_scalar, resnet2d, resnet_t3, wb
 
 
 class ResnetBlock2D(nn.Module):
@@ -35,11 +28,7 @@ class ResnetBlock2D(nn.Module):
         self.conv_shortcut = nn.Conv2d(cin, cout, 1) if cin != cout else None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        h = conv3x3(_gn(x, self.norm1, True), self.conv1)
-        h = _gn(h, self.norm2, True)
-        if self.conv_shortcut is not None:
-            x = ops.linear(x, bf16(lin_w(self.conv_shortcut)), bf16(self.conv_shortcut.bias))
-        return conv3x3(h, self.conv2, resid=x)
+        return resnet2d(x, self.norm1, self.conv1, self.norm2, self.conv2, self.conv_shortcut, conv=conv3x3)
 
 
 class TemporalResnetBlock(nn.Module):
@@ -54,10 +43,7 @@ class TemporalResnetBlock(nn.Module):
 
     def forward(self, x: torch.Tensor, num_frames: int) -> torch.Tensor:
         N, H, W, C = x.shape
-        b = N // num_frames
-        h = conv_t3(_gn(x, self.norm1, True, num_frames).view(N, H * W, C), self.conv1, b, num_frames)
-        h = _gn(h.view(N, H, W, C), self.norm2, True, num_frames).view(N, H * W, C)
-        return conv_t3(h, self.conv2, b, num_frames, resid=x.view(N, H * W, C)).view(N, H, W, C)
+        return resnet_t3(x.view(N, H * W, C), self.norm1, self.conv1, self.norm2, self.conv2, N // num_frames, num_frames).view(N, H, W, C)
 
 
 class _Mixer(nn.Module):
@@ -92,19 +78,7 @@ class Attention(nn.Module):
         self.to_out = nn.ModuleList([nn.Linear(ch, ch), nn.Dropout(0.0)])
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        N, H, W, C = x.shape
-        S = H * W
-        h = _gn(x, self.group_norm, False).view(N, S, C)
-        q = ops.linear(h, bf16(self.to_q.weight), bf16(self.to_q.bias))
-        k = ops.linear(h, bf16(self.to_k.weight), bf16(self.to_k.bias))
-        a = torch.empty(N, S, C, dtype=torch.bfloat16, device=x.device)
-        scores = torch.empty(S, S, dtype=torch.bfloat16, device=x.device)
-        for n in range(N):
-            ops.linear(q[n], k[n], out=scores)
-            ops.softmax_rows(scores, scale=float(C) ** -0.5, out=scores)
-            vt = ops.linear(bf16(self.to_v.weight), h[n])                                   # V^T = Wv h^T: no transpose pass; the bias rides below (rows of P sum to 1)
-            ops.linear(scores, vt, bf16(self.to_v.bias), out=a[n])
-        return ops.linear(a, bf16(self.to_out[0].weight), bf16(self.to_out[0].bias), epilogue=ops.EPI_RESID, resid=x.view(N, S, C)).view(N, H, W, C)
+        return attention_1head(x, self.group_norm, wb(self.to_q), wb(self.to_k), wb(self.to_v), wb(self.to_out[0]))
 
 
 class _Sampler(nn.Module):
@@ -149,7 +123,7 @@ class Encoder(nn.Module):
         h = self.mid_block.resnets[0](h)
         h = self.mid_block.attentions[0](h)
         h = self.mid_block.resnets[1](h)
-        return conv3x3(_gn(h, self.conv_norm_out, True), self.conv_out)
+        return conv3x3(groupnorm_rows(h, self.conv_norm_out, silu=True), self.conv_out)
 
 
 class TemporalDecoder(nn.Module):
@@ -186,7 +160,7 @@ class TemporalDecoder(nn.Module):
                 h = r(h, num_frames)
             if hasattr(blk, "upsamplers"):
                 h = conv3x3(h, blk.upsamplers[0].conv, upsample=True)
-        h = _gn(h, self.conv_norm_out, True)
+        h = groupnorm_rows(h, self.conv_norm_out, silu=True)
         co, conv, tconv = self.out_channels, self.conv_out, self.time_conv_out
 
         def build_out():                                                      # 3 output channels padded to 8: the temporal row gather moves 16-byte granules
@@ -243,7 +217,7 @@ class AutoencoderKLTemporalDecoder(nn.Module):
         if not x.is_cuda:
             raise ops.HipOnly("AutoencoderKLTemporalDecoder.encode: GPU tensors only")
         h = self.encoder(x.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous())
-        moments = ops.linear(h, bf16(lin_w(self.quant_conv)), bf16(self.quant_conv.bias)).permute(0, 3, 1, 2)
+        moments = ops.linear(h, *wb(self.quant_conv)).permute(0, 3, 1, 2)
         return _EncodeOut(DiagonalGaussianDistribution(moments))
 
     @torch.no_grad()

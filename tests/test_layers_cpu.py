@@ -1,6 +1,8 @@
 """`layers.WeightCache` on plain CPU tensors (no library load): when a derived weight is served, when it is rebuilt, and when its entry goes;
-plus the import graph -- the encoders do not pull in a UNet file."""
+plus the import graph -- the encoders do not pull in a UNet file, the SVD UNet does not pull in the DynamiCrafter one, `layers` pulls in no model file --
+the one FeedForward / GEGLU class the UNets share, and the SVD UNet's and VAE's checkpoint layout (tests/golden/svd_keys.json)."""
 import gc
+import json
 import os
 import subprocess
 import sys
@@ -134,8 +136,56 @@ def test_clear():
     assert b.calls == 3
 
 
+MODEL_FILES = ("dynamicrafter", "dynamicrafter_vae", "svd", "svd_unet", "svd_vae", "cogvideox", "cogvideox_vae", "attn_processor", "cama", "t5", "clip_vision",
+               "encoders", "text_embedder", "openclip_text", "rag", "dynamicrafter_pipeline")
+
+
 def test_encoders_do_not_import_a_unet_file():
-    code = ("import sys, motionrag_amd.t5, motionrag_amd.clip_vision, motionrag_amd.encoders, motionrag_amd.text_embedder, motionrag_amd.openclip_text; "
-            "sys.exit(1 if 'motionrag_amd.dynamicrafter' in sys.modules else 0)")
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr or "motionrag_amd.dynamicrafter was imported"
+    for imports, absent in ((("t5", "clip_vision", "encoders", "text_embedder", "openclip_text"), ("dynamicrafter",)),
+                            (("svd_unet",), ("dynamicrafter",)),
+                            (("layers",), MODEL_FILES)):
+        code = (f"import sys, {', '.join('motionrag_amd.' + m for m in imports)}; "
+                f"bad = [m for m in {absent!r} if 'motionrag_amd.' + m in sys.modules]; print(bad); sys.exit(1 if bad else 0)")
+        r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr or f"importing {imports} imported {r.stdout}"
+
+
+def test_one_feed_forward_class():
+    from motionrag_amd import dynamicrafter, layers, svd_unet
+    assert dynamicrafter.FeedForward is svd_unet.FeedForward is layers.FeedForward
+    assert dynamicrafter.GEGLU is svd_unet.GEGLU is layers.GEGLU
+    assert dynamicrafter.TembBank is layers.TembBank and dynamicrafter.temb_proj is layers.temb_proj
+    ff = layers.FeedForward(8, dim_out=16, mult=2)
+    assert {k: tuple(v.shape) for k, v in ff.state_dict().items()} == {"net.0.proj.weight": (32, 8), "net.0.proj.bias": (32,), "net.2.weight": (16, 16), "net.2.bias": (16,)}
+    holder = nn.Module()
+    holder.ff, holder.other = ff, nn.Linear(8, 8)
+    layers.set_ff_precision(holder, "fp8", sites=("ff2",))
+    layers.set_ff_fusion(holder, True)
+    assert getattr(ff, layers.FF_SITES_ATTR) == ("ff2",) and getattr(ff, layers.FF_FUSION_ATTR) is True
+    assert not hasattr(holder.other, layers.FF_SITES_ATTR) and not hasattr(holder.other, layers.FF_FUSION_ATTR)
+    layers.set_ff_precision(holder, "bf16")
+    layers.set_ff_fusion(holder, False)
+    assert getattr(ff, layers.FF_SITES_ATTR) == () and getattr(ff, layers.FF_FUSION_ATTR) is False
+
+
+def svd_layouts():
+    """sorted (key, shape) lists of the reduced SVD UNet (tests/test_oracle_golden.svd_tiny, plain and with the motion adapters installed) and of the reduced
+    and the default temporal-decoder VAE (tests/test_gpu_svd_vae.py)"""
+    from motionrag_amd import svd, svd_unet, svd_vae
+    cfg = dict(in_channels=8, out_channels=4, block_out_channels=(64, 128), addition_time_embed_dim=64, projection_class_embeddings_input_dim=192,
+               layers_per_block=1, cross_attention_dim=64, num_attention_heads=(1, 2))
+    unet = svd_unet.UNetSpatioTemporalConditionModel(**cfg)
+    mods = {"unet": svd_unet.UNetSpatioTemporalConditionModel(**cfg), "unet_motion": unet,
+            "vae_64_128": svd_vae.AutoencoderKLTemporalDecoder(block_out_channels=(64, 128), layers_per_block=1), "vae_default": svd_vae.AutoencoderKLTemporalDecoder()}
+    names = [n for n in unet.attn_processors if "temporal_transformer_blocks" not in n and n.endswith("attn2.processor")]
+    svd.set_attention_processors(unet, names, 64, {n: dict(unet.named_modules())[n[: -len(".processor")]].to_q.in_features for n in names})
+    return {name: [[k, list(v.shape)] for k, v in sorted(m.state_dict().items())] for name, m in mods.items()}
+
+
+def test_svd_checkpoint_layout():
+    with open(os.path.join(ROOT, "tests", "golden", "svd_keys.json")) as f:
+        want = json.load(f)
+    got = svd_layouts()
+    assert sorted(got) == sorted(want)
+    for name in want:
+        assert got[name] == want[name], name

@@ -5,8 +5,9 @@
 Every rank opens cuda:0 and the ranks talk through gloo (dist.FrameParallel stages GPU tensors through the host on a gloo group), so the Python path is the
 multi-GPU one except for the transport.  Each rank builds the reduced UNet of tests/golden/dc_unet.npz, runs the forward unsharded and sharded (twice), and
 checks: shape, finiteness, the same bits on every rank and from run to run, the golden bound of tests/test_gpu_unet.py (rel_l2 3e-2), and that sharding moves
-the result by no more than the bf16 model's own distance from the fp32 golden output.  Rank 0 prints ONE JSON line; the first failure ends the process with a
+the result by no more than the bf16 model's own distance from the fp32 golden output.  Rank 0 prints ONE JSON line (with the sha1 of its sharded and unsharded output bytes, to compare two trees); the first failure ends the process with a
 non-zero status before anything else is launched.  Says nothing about multi-GPU step time (unmeasured on hardware)."""
+import hashlib
 import json
 import os
 import sys
@@ -82,7 +83,8 @@ def main():
         if not same:
             fail("the ranks' outputs differ in bits")
         if rank == 0:
-            print(json.dumps({"world": world, "shape": list(first.shape), "finite": True, "same_bits_on_all_ranks": same, "repeatable": True,
+            sha1 = lambda t: hashlib.sha1(t.cpu().contiguous().view(torch.uint8).numpy().tobytes()).hexdigest()
+            print(json.dumps({"world": world, "sha1_sharded": sha1(first), "sha1_unsharded": sha1(plain), "shape": list(first.shape), "finite": True, "same_bits_on_all_ranks": same, "repeatable": True,
                               "rel_fro_sharded_vs_golden": e_golden, "rel_fro_unsharded_vs_golden": e_plain, "rel_fro_sharded_vs_unsharded": e_shard,
                               "golden_bound": GOLDEN_BOUND, "launches": {k: v for k, v in d.counts.items() if k.startswith("GN_")}}), flush=True)
     finally:
