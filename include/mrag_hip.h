@@ -320,7 +320,8 @@ typedef struct mrag_attn_args {
   const void* V;
   void* O;         /* element (b,s,h,d) at O + b*o_sb + s*o_ss + h*64 + d   */
   const void* resid;   /* same addressing as O, or NULL                     */
-  const uint8_t* mask; /* [Sq, Skv] bytes, nonzero = blocked, or NULL       */
+  const uint8_t* mask; /* [Sq, Skv] bytes, nonzero = blocked, or NULL.  Blocked keys may lie anywhere in a row, whole leading 64-key tiles
+                          included.  A row with NO open key is unspecified: the kernel writes NaN there (0 / 0; resid does not rescue it). */
   int64_t q_sb, q_ss, q_sh;
   int64_t k_sb, k_ss, k_sh;
   int64_t v_sb, v_ss, v_sh;
@@ -342,7 +343,12 @@ typedef struct mrag_attn_args {
   const float* bias;       /* additive score bias, fp32 [H, Sq, Skv] (head stride bias_sh elements, shared by the batch), or NULL:
                               softmax(scale * Q K^T + bias [masked]) V.  T5's relative position bias (transformers T5Attention:
                               `scores += position_bias`, scale = 1) -- the prompt encoder of the CogVideoX path.
-                              Takes the per-score path of the 32x32x16 kernel, like a mask.                                        */
+                              Takes the per-score path of the 32x32x16 kernel, like a mask.
+                              An entry of -inf blocks its key, and so does any entry so low that scale * q.k + bias falls below the
+                              first-tile floor of -16384 in log2 units (about -11 356 in natural units: finfo(float32).min and the
+                              customary -1e9 are far below it); a finite soft mask above the floor is an ordinary score.  Blocked
+                              entries may lie anywhere, whole leading 64-key tiles included (a left-padded T5 attention_mask).
+                              A row all of whose keys are blocked is unspecified, as for `mask`: the kernel writes NaN.              */
   int64_t bias_sh;
 } mrag_attn_args;
 enum { MRAG_ATTN_TUNE_NO_TINY = 1,   /* never take the <= 16-key one-wave-per-pair kernel          */

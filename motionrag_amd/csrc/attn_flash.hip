@@ -255,7 +255,12 @@ __device__ __forceinline__ void softmax_tile(const AttnP& p, const int skv, cons
   // deferred rescale: move the running max only on the first tile or when a row grew past THR
   const bool first = (t == 0);
   if (first || __any(tm > kThr)) {
-    float delta = first ? fmaxf(tm, -1e30f) : fmaxf(tm, 0.f);
+    // First-tile floor.  A row whose first tile is fully blocked has tm = -inf and must start somewhere finite.  Masked / biased launches start it at
+    // -2^14: exact in bf16, and the scores of the next tiles come out of the MFMA chain as S + 16384 with S kept to 2^-9 log2 units (0.07 % in P, below
+    // P's own bf16 rounding); the row's first open tile then re-centres it through the tm > kThr branch (alpha = exp2(-delta) = 0 times an O and l that
+    // are still zero).  From -1e30 the sum S + 1e30 lost S altogether and the row came out as uniform attention over that tile.
+    constexpr float kFloor = HAS_MASK ? -16384.f : -1e30f;
+    float delta = first ? fmaxf(tm, kFloor) : fmaxf(tm, 0.f);
     // the shift lives in a bf16 MFMA operand: round the new running max to bf16 and move by the EXACT difference (both ends are
     // bf16 values, their fp32 difference is exact), so O / l / P all see the same shift.  Rows that do not move keep delta == 0.
     const float m_new = bf_round(r.m + delta);

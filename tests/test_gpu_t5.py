@@ -34,8 +34,12 @@ def test_rmsnorm_bias_attention_and_gated_gelu_tanh(hip):
     want = torch.einsum("bhqk,bkhd->bqhd", want, v.float()).reshape(B, S, H * 64)
     got = ops.attention(q.to(DEV), k.to(DEV), v.to(DEV), scale=1.0, bias=bias.to(DEV))
     assert rel(got, want) <= 1e-2
-    got_m = ops.attention(q.to(DEV), k.to(DEV), v.to(DEV), scale=1.0, bias=bias.to(DEV), mask=(torch.rand(S, S, generator=g) < 0.3).to(DEV))   # bias AND mask
-    assert torch.isfinite(got_m.float()).all()
+    mask = torch.rand(S, S, generator=g) < 0.3                                    # bias AND mask
+    assert not mask.all(dim=-1).any()
+    got_m = ops.attention(q.to(DEV), k.to(DEV), v.to(DEV), scale=1.0, bias=bias.to(DEV), mask=mask.to(DEV))
+    want_m = torch.softmax((torch.einsum("bqhd,bkhd->bhqk", q.float(), k.float()) + bias[None]).masked_fill(mask[None, None], float("-inf")), dim=-1)
+    want_m = torch.einsum("bhqk,bkhd->bqhd", want_m, v.float()).reshape(B, S, H * 64)
+    assert rel(got_m, want_m) <= 1e-2
     # gated GELU (tanh): [value | gate] = [wi_1 | wi_0]
     M, K, F_ = 300, 128, 256
     h = torch.randn(M, K, generator=g).to(torch.bfloat16)
