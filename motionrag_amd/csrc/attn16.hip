@@ -25,12 +25,9 @@
 // K / V tiles of 64 keys ride a 3-stage LDS-DMA ring like attn_flash.hip's (scalar-base global_load_lds, counted vmcnt, raw s_barrier);
 // V's 32-byte chunks are XOR-swizzled by (key >> 1) & 3 on the DMA source so the transposed reads are conflict-free.
 #include "attn_common.h"
-#include "../../include/mrag_hip.h"
 
 namespace {
 
-constexpr int KVB = 64;                // keys per compute tile
-constexpr int TILE_BYTES = KVB * 128;
 // LDS: K ring of NS stages, then the V ring
 constexpr float kBig = 16777216.0f;    // lazy-max trigger: a lane's partial row sum of one tile above 2^24
 
@@ -495,14 +492,9 @@ static int launch16_plain(hipStream_t s, AttnP p) {
 
 template <int QB, int NW, int NS>
 static int launch16_split(hipStream_t s, AttnP p, const SplitPlan* pl, void* workspace) {
-  const int nbh = p.B * p.H;
   const size_t lds = 2 * NS * TILE_BYTES;
-  p.n_qtiles = pl->n_full;
-  p.n_main = pl->n_full * nbh;
-  p.kv_splits = pl->splits; p.chunk_keys = pl->chunk_keys; p.rem_rows = pl->rem_rows; p.tile_rows = NW * QB * 16;
-  p.part_o = (float*)workspace;
-  p.part_ml = (float2*)((char*)workspace + (size_t)nbh * pl->splits * pl->rem_rows * 64 * sizeof(float));
-  const int rc = launch_dyn_lds(attn16_kernel<QB, NW, NS, true>, dim3(p.n_main + nbh * pl->splits), dim3(NW * 64), lds, s, p);
+  attn_fill_split(p, *pl, workspace, NW * QB * 16);
+  const int rc = launch_dyn_lds(attn16_kernel<QB, NW, NS, true>, dim3(p.n_main + p.B * p.H * pl->splits), dim3(NW * 64), lds, s, p);
   if (rc != MRAG_OK) return rc;
   MRAG_COUNT(MRAG_K_ATTN16_KSPLIT);
   return mrag_launch_attn_combine(s, p);
@@ -514,7 +506,7 @@ static int launch16_split(hipStream_t s, AttnP p, const SplitPlan* pl, void* wor
 //           5-7 % behind with the checked loop of round 3; with the optimistic sweep 2.6 % ahead in a cold microbenchmark and 1.5 % behind inside
 //           the denoise step (attn_common.h) -- measured in the step, QB = 3 stays.
 // Retired by measurement and pruned: 32 rows per wave in 8-wave workgroups, fragment prefetching at 150 VGPRs (-4 %), 128-key LDS stages (-1 %).
-int mrag_launch_attn16(hipStream_t s, AttnP p, const SplitPlan* pl, void* workspace, int qb) {
+MRAG_FAMILY_LAUNCHER mrag_launch_attn16(hipStream_t s, AttnP p, const SplitPlan* pl, void* workspace, int qb) {
   if (p.mask || p.Sq <= 128 || p.Skv < 4 * KVB) return MRAG_ENOTSUP;
   if ((long long)p.Skv * p.k_ss * 2 >= 0xffffffffLL || (long long)p.Skv * p.v_ss * 2 >= 0xffffffffLL) return MRAG_ENOTSUP;   // walked 32-bit DMA offsets
   if (pl) {

@@ -1,11 +1,10 @@
-// attn_flash.hip -- head_dim-64 bf16 attention forward for gfx950 (flash-style, online softmax).
+// attn_flash.hip -- head_dim-64 bf16 attention forward on v_mfma_f32_32x32x16_bf16 (flash-style, online softmax): attn_fwd_kernel and its launcher.
 //
-//   O[b, q, h, :] = resid + out_scale * softmax(Q K^T * scale  [masked])  V
+//   O[b, q, h, :] = resid + out_scale * softmax(Q K^T * scale  [masked, + bias])  V
 //
-// One kernel family serves every F.scaled_dot_product_attention call site of the MotionRAG hot path
-// (include/mrag_hip.h): the 17 776-token CogVideoX joint attention, the 25-key motion
-// ("ip") cross-attention with its fused `hidden + scale * ip` update, the Perceiver resampler
-// (25 queries x 1 593 keys) and the block-causal CAMA encoder (bool mask).
+// mrag_attn_fwd_bf16 (attn_bf16.hip) sends here what the other families do not take: short and cross-attention launches (the 25-key motion ("ip")
+// cross-attention with its fused `hidden + scale * ip` update, the Perceiver resampler's 25 queries x 1 593 keys), everything with a byte mask or a score
+// bias (the block-causal CAMA encoder, T5), and long unmasked sequences when the 16x16x32 family (attn16.hip) is switched off or refuses.
 //
 // CDNA4 design:
 //   * v_mfma_f32_32x32x16_bf16 with SWAPPED products: S^T = K . Q^T and O^T = V^T . P^T, so a lane
@@ -25,18 +24,13 @@
 //     rescale): the rare path rescales O, l, the pending S' and the prefetched S' together;
 //   * grid = q-tiles x (b, h) with an XCD-aware order: all q-tiles of one (b, h) run on one XCD,
 //     so its K/V (4.5 MB at S = 17 776) streams from that XCD's L2.
-#include "common.h"
 #include <type_traits>
-#include "../../include/mrag_hip.h"
-
 #include "attn_common.h"
 
 namespace {
 
 constexpr float kThr = 5.0f;          // deferred-rescale threshold in log2 units (P <= 32)
-constexpr int KVB = 64;               // keys per tile
-constexpr int TILE_BYTES = KVB * 128; // one K (or V) tile
-constexpr int NS = 4;   // LDS ring stages per operand (DMA runs D = NS-1 tiles ahead); 2 x 64 KB fit two workgroups per CU
+constexpr int NS = 4;  // LDS ring stages per operand (DMA runs D = NS-1 tiles ahead); 2 x 64 KB fit two workgroups per CU
 constexpr int V_BASE = NS * TILE_BYTES;  // LDS: K stages 0..NS-1, then V stages 0..NS-1
 
 __device__ __forceinline__ bf16x8 scale_frag(u32x4 raw, float s) {
@@ -229,8 +223,8 @@ __device__ __forceinline__ void softmax_tile(const AttnP& p, const int skv, cons
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int key = kbase_idx + (i & 3) + 8 * (i >> 2);
-        if (key < p.Skv) s0[i] = fmaf(brow[key], 1.4426950408889634f, s0[i]);
-        if (key + 32 < p.Skv) s1[i] = fmaf(brow[key + 32], 1.4426950408889634f, s1[i]);
+        if (key < p.Skv) s0[i] = fmaf(brow[key], kLog2e, s0[i]);
+        if (key + 32 < p.Skv) s1[i] = fmaf(brow[key + 32], kLog2e, s1[i]);
       }
     }
   }
@@ -309,7 +303,7 @@ __device__ __forceinline__ void softmax_tile(const AttnP& p, const int skv, cons
 // SHORTKV: key sets of at most one tile (motion tokens, text, temporal frames) -- same code, no barrier stagger; a separate
 // instantiation so that profiles list the HBM-bound small-KV launches apart from the MFMA-bound long-sequence ones.
 // KVSPLIT: the launch's last workgroups (blockIdx >= n_main) each scan ONE CHUNK of the keys for the ragged last query tile of a
-// (b, h) pair and leave (unnormalised O, running max, row sum) in the workspace for attn_combine_kernel -- see launch_attn_split.
+// (b, h) pair and leave (unnormalised O, running max, row sum) in the workspace for attn_combine_kernel (attn_bf16.hip) -- see launch_attn_split.
 template <int NW, bool HAS_MASK, bool SHORTKV = false, bool KVSPLIT = false>
 __global__ __launch_bounds__(NW * 64, (NW == 8 && !HAS_MASK) ? 4 : 1) void attn_fwd_kernel(const AttnP p) {
   constexpr int PPW = NW >= 8 ? 1 : 8 / NW;  // 1 KiB DMA pieces per wave per K (or V) tile
@@ -521,7 +515,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && !HAS_MASK) ? 4 : 1) void attn_
   }
 }
 
-
 template <int NW, bool SHORTKV = false>
 int launch_attn(hipStream_t s, AttnP p) {
   p.n_qtiles = (p.Sq + NW * 32 - 1) / (NW * 32);
@@ -533,362 +526,21 @@ int launch_attn(hipStream_t s, AttnP p) {
   return MRAG_OK;
 }
 
-// ---------------------------------------------------------------------------------------------- key-split tail
-// Long-sequence launches are many rounds of 512 resident workgroups (2 per CU) and the LAST round is what the ragged query tile of each
-// (b, h) pair leaves: B*H workgroups that each scan ALL keys for Sq % 256 rows.  At the BASELINE shape (B*H = 96, Sq = 17 776 =
-// 69 x 256 + 112) those 96 workgroups are 1.4 % of the launch's work and 4 % of its time (tools/tail_probe.py: 7.33 ms for the 6624
-// full tiles, 7.63 ms with the ragged ones).  Splitting THEIR keys into `kv_splits` chunks turns the 96 long stragglers into ~512 short
-// workgroups that drain into the slots the last full round frees; each leaves (unnormalised O, running max, row sum) in a caller-provided
-// workspace and attn_combine_kernel merges the chunks, applies out_scale / resid and writes bf16 -- the same online-softmax algebra as
-// between two key tiles, carried through HBM instead of registers.
-}  // namespace
-
-SplitPlan mrag_plan_kv_split(int B, int H, int Sq, int Skv, int tile_rows, int slots) {
-  // tile_rows: query rows per workgroup (256: attn_flash.hip; 192: attn16.hip); slots: workgroups resident on the chip (2 or 3 per CU)
-  SplitPlan pl;
-  const int rem = Sq % tile_rows, n_full = Sq / tile_rows, nt = (Skv + KVB - 1) / KVB;
-  const long long nbh = (long long)B * H;
-  int want = (int)(slots / nbh);
-  if (want > 8) want = 8;
-  if (rem == 0 || nbh * n_full < 1024 || want < 2 || nt < 8 * want) return pl;
-  const int tpc = (nt + want - 1) / want;
-  const int chunk = tpc * KVB, splits = (Skv + chunk - 1) / chunk;
-  if (splits < 2 || Skv - (splits - 1) * chunk < KVB) return pl;       // every chunk must hold one whole (slid-back) tile
-  pl.splits = splits; pl.chunk_keys = chunk; pl.rem_rows = rem; pl.n_full = n_full;
-  pl.bytes = (size_t)nbh * splits * rem * (64 * sizeof(float) + sizeof(float2));
-  return pl;
-}
-
-namespace {
-
-__global__ __launch_bounds__(256) void attn_combine_kernel(const AttnP p) {
-  const long long idx = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);   // (b*H + h, row of the ragged tile); 16 lanes x 4 columns per row
-  if (idx >= (long long)p.B * p.H * p.rem_rows) return;
-  const int bh = (int)(idx / p.rem_rows), row = (int)(idx % p.rem_rows), d = (threadIdx.x & 15) * 4;
-  const long long u0 = (long long)bh * p.kv_splits;
-  float M = -INFINITY;
-  for (int c = 0; c < p.kv_splits; ++c) M = fmaxf(M, p.part_ml[(u0 + c) * p.rem_rows + row].x);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  float l = 0.f;
-  for (int c = 0; c < p.kv_splits; ++c) {
-    const long long pr = (u0 + c) * p.rem_rows + row;
-    const float2 ml = p.part_ml[pr];
-    const float w = __builtin_amdgcn_exp2f(ml.x - M);
-    l += w * ml.y;
-    acc += *(const f32x4*)(p.part_o + pr * 64 + d) * w;
-  }
-  const float inv = p.out_scale / l;
-  const int b = bh / p.H, h = bh % p.H;
-  const long long off = (long long)b * p.o_sb + (long long)(p.n_qtiles * p.tile_rows + row) * p.o_ss + h * 64 + d;
-  float v[4] = {acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv};
-  if (p.resid) {
-    const u32x2 rr = *(const u32x2*)(p.resid + off);
-    v[0] += __uint_as_float(rr[0] << 16); v[1] += __uint_as_float(rr[0] & 0xffff0000u);
-    v[2] += __uint_as_float(rr[1] << 16); v[3] += __uint_as_float(rr[1] & 0xffff0000u);
-  }
-  u32x2 out;
-  out[0] = pack_bf2(v[0], v[1]);
-  out[1] = pack_bf2(v[2], v[3]);
-  *(u32x2*)(p.O + off) = out;
-}
-
+// Key-split tail (attn_bf16.hip: mrag_plan_kv_split): the launch's last workgroups each scan one chunk of the keys for the ragged last query tile of a
+// (b, h) pair; the merge kernel finishes those rows.
 int launch_attn_split(hipStream_t s, AttnP p, const SplitPlan& pl, void* workspace) {
-  const int nbh = p.B * p.H;
-  p.n_qtiles = pl.n_full;
-  p.n_main = pl.n_full * nbh;
-  p.kv_splits = pl.splits; p.chunk_keys = pl.chunk_keys; p.rem_rows = pl.rem_rows; p.tile_rows = 256;
-  p.part_o = (float*)workspace;
-  p.part_ml = (float2*)((char*)workspace + (size_t)nbh * pl.splits * pl.rem_rows * 64 * sizeof(float));
+  attn_fill_split(p, pl, workspace, 256);
   const size_t lds = 2 * NS * TILE_BYTES;
-  const int rc = launch_dyn_lds(attn_fwd_kernel<8, false, false, true>, dim3(p.n_main + nbh * pl.splits), dim3(512), lds, s, p);
+  const int rc = launch_dyn_lds(attn_fwd_kernel<8, false, false, true>, dim3(p.n_main + p.B * p.H * pl.splits), dim3(512), lds, s, p);
   if (rc != MRAG_OK) return rc;
   MRAG_COUNT(MRAG_K_ATTN_FLASH_KSPLIT);
-  MRAG_LAUNCH(attn_combine_kernel, dim3((unsigned)(((long long)nbh * pl.rem_rows + 15) / 16)), dim3(256), 0, s, p);
-  MRAG_LAUNCH_CHECK();
-  MRAG_COUNT(MRAG_K_ATTN_COMBINE);
-  return MRAG_OK;
+  return mrag_launch_attn_combine(s, p);
 }
 
 }  // namespace
 
-int mrag_launch_attn_combine(hipStream_t s, const AttnP& p) {
-  MRAG_LAUNCH(attn_combine_kernel, dim3((unsigned)(((long long)p.B * p.H * p.rem_rows + 15) / 16)), dim3(256), 0, s, p);
-  MRAG_LAUNCH_CHECK();
-  MRAG_COUNT(MRAG_K_ATTN_COMBINE);
-  return MRAG_OK;
-}
-
-extern "C" int64_t mrag_attn_workspace_bytes(int32_t B, int32_t H, int32_t Sq, int32_t Skv) {
-  if (B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0) return 0;
-  const size_t a = mrag_plan_kv_split(B, H, Sq, Skv, 256, 512).bytes, b = mrag_plan_kv_split(B, H, Sq, Skv, mrag_attn16_rows(mrag_attn16_qb(Sq)), mrag_attn16_slots(mrag_attn16_qb(Sq))).bytes;
-  return (int64_t)(a > b ? a : b);      // either kernel family's tail plan fits
-}
-
-// ---------------------------------------------------------------------------------------------- tiny sequences
-// Temporal attention of the UNets (TemporalTransformer / TemporalBasicTransformerBlock: 14-16 frames per pixel, head_dim 64, one
-// (pixel, head) pair = 6 KB of Q/K/V) is pure data movement: the 64-key tiles of the flash kernel above would pad every pair 4-8x.
-// Here one wavefront owns a pair: Q and K go from global memory straight into 16x16x32 MFMA operand registers (row = lane & 15,
-// 16-byte chunk = lane >> 4), S^T = K.Q^T is 2 MFMAs, the softmax over <= 16 keys is 4 registers x 4 lane groups, P^T is re-laid into
-// the B operand with two cross-lane moves, V is staged (2 KB, row pitch 144 B) in a per-wave LDS slot and read column-wise for the
-// V^T operand of the four O^T = V^T.P^T MFMAs.  No barrier: every LDS byte is written and read by the same wave.
-__global__ __launch_bounds__(256) void attn_tiny_kernel(const AttnP p) {
-  __shared__ __attribute__((aligned(16))) char vsm[4][16 * 144];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r16 = lane & 15, kq = lane >> 4;
-  char* vs = vsm[wave];
-  const int total = p.B * p.H;
-  for (int pair = blockIdx.x * 4 + wave; pair < total; pair += gridDim.x * 4) {
-    const int b = pair / p.H, h = pair - b * p.H, kb = b / p.kv_div;
-    const bf16_t* Qp = p.Q + (long long)b * p.q_sb + (long long)h * p.q_sh;
-    const bf16_t* Kp = p.K + (long long)kb * p.k_sb + (long long)h * p.k_sh;
-    const bf16_t* Vp = p.V + (long long)kb * p.v_sb + (long long)h * p.v_sh;
-    const int qrow = r16 < p.Sq ? r16 : p.Sq - 1, krow = r16 < p.Skv ? r16 : p.Skv - 1;   // clamped rows are masked / never stored
-    const bf16x8 q0 = *(const bf16x8*)(Qp + (long long)qrow * p.q_ss + kq * 8), q1 = *(const bf16x8*)(Qp + (long long)qrow * p.q_ss + 32 + kq * 8);
-    const bf16x8 k0 = *(const bf16x8*)(Kp + (long long)krow * p.k_ss + kq * 8), k1 = *(const bf16x8*)(Kp + (long long)krow * p.k_ss + 32 + kq * 8);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {                      // V: 16 rows x 8 chunks of 16 bytes
-      const int c = lane + 64 * j, row = c >> 3, col = c & 7;
-      const int vrow = row < p.Skv ? row : p.Skv - 1;
-      *(u32x4*)(vs + row * 144 + col * 16) = *(const u32x4*)(Vp + (long long)vrow * p.v_ss + col * 8);
-    }
-    f32x4 st = {0.f, 0.f, 0.f, 0.f};
-    st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, q0, st, 0, 0, 0);
-    st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, q1, st, 0, 0, 0);      // st[i] = S[q = r16][key = 4 kq + i]
-    float sv[4], m = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      sv[i] = (4 * kq + i < p.Skv) ? st[i] * p.qscale : -INFINITY;
-      m = fmaxf(m, sv[i]);
-    }
-    m = fmaxf(m, __shfl_xor(m, 16));
-    m = fmaxf(m, __shfl_xor(m, 32));
-    float l = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { sv[i] = __builtin_amdgcn_exp2f(sv[i] - m); l += sv[i]; }
-    l += __shfl_xor(l, 16);
-    l += __shfl_xor(l, 32);
-    const unsigned own0 = pack_bf2(sv[0], sv[1]), own1 = pack_bf2(sv[2], sv[3]);
-    const unsigned a0 = __shfl(own0, lane + 16), a1 = __shfl(own1, lane + 16), c0 = __shfl(own0, lane + 32), c1 = __shfl(own1, lane + 32);
-    u32x4 pw = {0u, 0u, 0u, 0u};                        // P^T as B operand: lane (q, kq) holds keys 8 kq .. 8 kq + 7
-    if (kq == 0) pw = u32x4{own0, own1, a0, a1};
-    else if (kq == 1) pw = u32x4{a0, a1, c0, c1};
-    const bf16x8 pb = __builtin_bit_cast(bf16x8, pw);
-    const float inv = p.out_scale / l;
-    bf16_t* Op = p.O + (long long)b * p.o_sb + (long long)r16 * p.o_ss + h * 64;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      u32x4 vw = {0u, 0u, 0u, 0u};                      // V^T as A operand: lane (d = 16 dt + r16, kq) holds keys 8 kq .. 8 kq + 7
-      if (kq < 2) {
-        const unsigned short* col = (const unsigned short*)(vs + (8 * kq) * 144 + (16 * dt + r16) * 2);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) vw[e] = (unsigned)col[(2 * e) * 72] | ((unsigned)col[(2 * e + 1) * 72] << 16);
-      }
-      f32x4 o = {0.f, 0.f, 0.f, 0.f};
-      o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vw), pb, o, 0, 0, 0);   // o[i] = O[q = r16][d = 16 dt + 4 kq + i]
-      if (r16 < p.Sq) {
-        u32x2 out = {pack_bf2(o[0] * inv, o[1] * inv), pack_bf2(o[2] * inv, o[3] * inv)};
-        *(u32x2*)(Op + 16 * dt + 4 * kq) = out;
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------- folded motion-adapter branch
-// hidden += scale * softmax(scores / 8) . V_ip with scores = hidden . M^T already produced by the GEMM, M = K_ip . W_q_ip per head
-// (see include/mrag_hip.h: mrag_ip_attn_folded_bf16).  One wavefront owns 16 rows x one head at a time: the 32 (25 valid) scores of a
-// (row, head) are 64 contiguous bytes = the 16x16x32 B-operand layout (row = lane & 15, 8 keys per lane >> 4) straight from global
-// memory, the softmax is 8 registers x 4 lane groups, V^T of the block's heads sits transposed in LDS as the A operand, and
-// O^T = V^T . P^T.  HBM-bound (546 MB per launch at the DiT shape: 109 MB of scores, 218 MB of `hidden` in and out), so the layout is chosen for the
-// MEMORY side (round 5): the four MFMAs of a head take V^T rows in the PERMUTED feature order
-//     d(m, t) = 8 (m >> 2) + 4 (t & 1) + (m & 3) + 32 (t >> 1)          m = A row of MFMA t
-// so that lane (row, kq) ends up with features 8 kq .. 8 kq + 7 (MFMAs 0, 1) and 32 + 8 kq .. 32 + 8 kq + 7 (MFMAs 2, 3): `hidden` is read and written
-// as TWO 16-byte accesses per lane, each instruction covering 64 contiguous bytes per row, instead of the four 8-byte accesses (32 contiguous bytes per
-// row and instruction) the natural order d = 16 t + m gives -- half the vector-memory instructions and twice the bytes per cache-line request.  The V^T
-// image is XOR-swizzled by (d >> 3) & 3 on its 16-byte key chunks: the permuted rows of one MFMA then hit 16 distinct bank groups (the plain
-// image is 4-way conflicted for either order).
-struct IpFoldP {
-  const bf16_t* scores; const bf16_t* v; bf16_t* o;
-  long long rows, s_ld, o_ld, v_bs, v_ks, rows_per_batch;
-  int H, keys, kv_div, ks;   // ks: elements between the heads' score blocks (32: 64-byte aligned blocks; 26: the packed form of the one-launch score GEMM)
-  float qscale, out_scale;
-};
-
-constexpr int IPFOLD_HG = 4;   // heads whose V^T image a workgroup keeps in LDS (4 KB each); MI355X, DiT shape: 16 -> 196 us, 8 -> 194, 4 -> 185 (more workgroups in flight)
-__global__ __launch_bounds__(256) void ip_attn_folded_kernel(const IpFoldP p) {
-  constexpr int HG = IPFOLD_HG;                            // heads per block
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16_t* vt = (bf16_t*)smem;                               // [HG][64 d][4 swizzled chunks of 8 keys]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r16 = lane & 15, kq = lane >> 4;
-  const int h0 = blockIdx.y * HG, kb = blockIdx.z;          // blockIdx.z = K/V batch (one V^T image per block)
-  const int nh = min(HG, p.H - h0);
-  for (int i = threadIdx.x; i < HG * 64 * 32 / 8; i += 256) ((u32x4*)vt)[i] = u32x4{0u, 0u, 0u, 0u};   // padding keys / heads
-  __syncthreads();
-  // Key SLOTS.  The four lanes of a (row, head) read the four ALIGNED 16-byte chunks that cover the head's score block: with the packed blocks (ks = 26: a
-  // block starts every 52 bytes) the block begins s = (ks h) mod 8 elements into its first chunk, so key k of head h sits in MFMA slot k + s -- the contraction
-  // does not care which slot a key occupies as long as the V^T image uses the same one, and the slots in front of / behind the block (neighbouring heads'
-  // scores) are masked.  ks = 32: s = 0, the round-5 layout.  (The first packed form read 16 bytes from 4-byte aligned addresses: + 9 us per launch.)
-  for (int i = threadIdx.x; i < p.keys * nh * 8; i += 256) {     // 16-byte chunk (key, head, 8 features) -> 8 transposed LDS elements
-    const int c8 = i & 7, hl = (i >> 3) % nh, key = (i >> 3) / nh;
-    const int slot = key + ((p.ks * (h0 + hl)) & 7);
-    const u32x4 raw = *(const u32x4*)(p.v + (long long)kb * p.v_bs + (long long)key * p.v_ks + (h0 + hl) * 64 + c8 * 8);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int d = c8 * 8 + e;                                  // (d >> 3) & 3 == c8 & 3
-      vt[(hl * 64 + d) * 32 + ((((slot >> 3) ^ (c8 & 3)) << 3) | (slot & 7))] = (bf16_t)((e & 1) ? (raw[e >> 1] >> 16) : (raw[e >> 1] & 0xffffu));
-    }
-  }
-  __syncthreads();
-  // A-operand addresses of the four MFMAs: V^T row d(r16, t), key chunk kq (swizzled by (d >> 3) & 3 = r16 >> 2)
-  const int dbase = 8 * (r16 >> 2) + (r16 & 3), kchunk = (kq ^ (r16 >> 2)) << 3;
-  // this K/V batch covers q batches [kb * kv_div, (kb + 1) * kv_div): rows [row_lo, row_hi)
-  const long long row_lo = (long long)kb * p.kv_div * p.rows_per_batch, row_hi = row_lo + (long long)p.kv_div * p.rows_per_batch;
-  for (long long g0 = row_lo + ((long long)blockIdx.x * 4 + wave) * 16; g0 < row_hi; g0 += (long long)gridDim.x * 64) {
-    const long long row = g0 + r16;
-    const long long rc = row < row_hi ? row : row_hi - 1;
-    // the row's scores and current values of the NEXT head are requested while this head is processed (latency-bound kernel)
-    u32x4 raw_n = *(const u32x4*)(p.scores + rc * p.s_ld + ((h0 * p.ks) & ~7) + kq * 8);   // (nontemporal loads of the scores measured no different: profiles/r6_ip_attn_folded_packed_aligned.txt)
-    u32x4 old_n[2];
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) old_n[hf] = *(const u32x4*)(p.o + rc * p.o_ld + h0 * 64 + 32 * hf + 8 * kq);
-    for (int hl = 0; hl < nh; ++hl) {
-      const int h = h0 + hl;
-      const u32x4 raw = raw_n;
-      bf16_t* op = p.o + rc * p.o_ld + h * 64;
-      const u32x4 old[2] = {old_n[0], old_n[1]};
-      if (hl + 1 < nh) {
-        raw_n = *(const u32x4*)(p.scores + rc * p.s_ld + (((h + 1) * p.ks) & ~7) + kq * 8);
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) old_n[hf] = *(const u32x4*)(op + 64 + 32 * hf + 8 * kq);
-      }
-      float sv[8], m = -INFINITY;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        sv[2 * e] = __uint_as_float(raw[e] << 16) * p.qscale;
-        sv[2 * e + 1] = __uint_as_float(raw[e] & 0xffff0000u) * p.qscale;
-      }
-      const int shift = (p.ks * h) & 7;                           // slot of key 0 (wave-uniform)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        if ((unsigned)(kq * 8 + e - shift) >= (unsigned)p.keys) sv[e] = -INFINITY;
-        m = fmaxf(m, sv[e]);
-      }
-      m = fmaxf(m, __shfl_xor(m, 16));
-      m = fmaxf(m, __shfl_xor(m, 32));
-      float l = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { sv[e] = __builtin_amdgcn_exp2f(sv[e] - m); l += sv[e]; }
-      l += __shfl_xor(l, 16);
-      l += __shfl_xor(l, 32);
-      const u32x4 pw = {pack_bf2(sv[0], sv[1]), pack_bf2(sv[2], sv[3]), pack_bf2(sv[4], sv[5]), pack_bf2(sv[6], sv[7])};
-      const bf16x8 pb = __builtin_bit_cast(bf16x8, pw);
-      const float inv = p.out_scale / l;
-      const bf16_t* vh = vt + hl * 64 * 32 + kchunk;
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {                            // features 32 hf + 8 kq .. + 7 of this lane's row
-        u32x4 nw;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {                             // MFMA t = 2 hf + q: features 32 hf + 8 kq + 4 q .. + 3
-          const bf16x8 va = *(const bf16x8*)(vh + (dbase + 4 * q + 32 * hf) * 32);
-          f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va, pb, acc, 0, 0, 0);     // acc[i] = out[row = r16][d = 32 hf + 8 kq + 4 q + i]
-          const unsigned o0 = old[hf][2 * q], o1 = old[hf][2 * q + 1];
-          nw[2 * q] = pack_bf2(__uint_as_float(o0 << 16) + acc[0] * inv, __uint_as_float(o0 & 0xffff0000u) + acc[1] * inv);
-          nw[2 * q + 1] = pack_bf2(__uint_as_float(o1 << 16) + acc[2] * inv, __uint_as_float(o1 & 0xffff0000u) + acc[3] * inv);
-        }
-        if (row < row_hi) *(u32x4*)(op + 32 * hf + 8 * kq) = nw;
-      }
-    }
-  }
-}
-
-extern "C" int mrag_ip_attn_folded_bf16(void* stream, const void* scores, const void* v, void* hidden, int32_t B, int64_t S, int32_t H, int32_t keys,
-                                        int32_t kv_batch_div, int64_t scores_ld, int64_t hidden_ld, int64_t v_batch_stride, int64_t v_key_stride,
-                                        float scale, float out_scale, int32_t key_stride) {
-  if (!scores || !v || !hidden || B <= 0 || S <= 0 || H <= 0 || keys <= 0 || keys > 32 || kv_batch_div <= 0 || B % kv_batch_div) return MRAG_EINVAL;
-  const int ks = key_stride == 0 ? 32 : key_stride;
-  if (ks < keys || ks > 32) return MRAG_EINVAL;
-  for (int h = 0; h < H && h < 8; ++h)                                            // a block's keys must fit the 32 slots of the aligned chunks that cover it ((ks h) mod 8 repeats with period <= 8)
-    if (((ks * h) & 7) + keys > 32) return MRAG_EINVAL;
-  if (scores_ld % 8 || hidden_ld % 8 || scores_ld < (((int64_t)(H - 1) * ks) & ~7LL) + 32 || hidden_ld < (int64_t)H * 64) return MRAG_EINVAL;   // a lane group reads the 32 elements from the aligned chunk that holds a block's start
-  if (((uintptr_t)scores & 15) || ((uintptr_t)hidden & 15) || ((uintptr_t)v & 15) || v_batch_stride % 8 || v_key_stride % 8) return MRAG_EINVAL;
-  IpFoldP p{};
-  p.scores = (const bf16_t*)scores; p.v = (const bf16_t*)v; p.o = (bf16_t*)hidden;
-  p.rows = (long long)B * S; p.s_ld = scores_ld; p.o_ld = hidden_ld; p.v_bs = v_batch_stride; p.v_ks = v_key_stride; p.rows_per_batch = S;
-  p.H = H; p.keys = keys; p.kv_div = kv_batch_div; p.ks = ks; p.qscale = scale * 1.4426950408889634f; p.out_scale = out_scale;
-  constexpr int HG = IPFOLD_HG;
-  const size_t lds = HG * 64 * 32 * sizeof(bf16_t);
-  const long long groups = ((long long)kv_batch_div * S + 63) / 64;
-  // ONE round of resident workgroups (each pays a V^T fill and then walks its share of the rows): the count the RUNTIME reports for this kernel's registers
-  // and LDS.  Until round 6 the grid assumed eight workgroups per CU from the LDS size alone; the kernel's 72 VGPRs allow seven -- 2 040 workgroups on 1 792
-  // slots, i.e. a second round for an eighth of them.
-  static int wg_per_cu = 0;                                  // (a property of the code object; the benign race writes the same value)
-  if (wg_per_cu == 0) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)ip_attn_folded_kernel, 256, lds) != hipSuccess || n <= 0) n = 4;
-    wg_per_cu = n;
-  }
-  const long long per = (256LL * wg_per_cu) / (((H + HG - 1) / HG) * (long long)(B / kv_batch_div));
-  const unsigned gx = (unsigned)(groups < (per > 1 ? per : 1) ? groups : (per > 1 ? per : 1));
-  const int rc = launch_dyn_lds(ip_attn_folded_kernel, dim3(gx, (unsigned)((H + HG - 1) / HG), (unsigned)(B / kv_batch_div)), dim3(256), lds, (hipStream_t)stream, p);
-  if (rc != MRAG_OK) return rc;
-  MRAG_COUNT(MRAG_K_IP_ATTN_FOLDED);
-  return MRAG_OK;
-}
-
-extern "C" int mrag_attn_fwd_bf16(void* stream, const mrag_attn_args* a) {
-  if (!a || !a->Q || !a->K || !a->V || !a->O) return MRAG_EINVAL;
-  if (a->B <= 0 || a->H <= 0 || a->Sq <= 0 || a->Skv <= 0 || a->kv_batch_div <= 0) return MRAG_EINVAL;
-  if (a->B % a->kv_batch_div != 0) return MRAG_EINVAL;
-  // 16-byte fragment / DMA loads and 8-byte stores
-  if (((uintptr_t)a->Q | (uintptr_t)a->K | (uintptr_t)a->V) & 15) return MRAG_EINVAL;
-  if ((a->q_sb | a->q_ss | a->q_sh | a->k_sb | a->k_ss | a->k_sh | a->v_sb | a->v_ss | a->v_sh) % 8 != 0) return MRAG_EINVAL;
-  if (((uintptr_t)a->O & 7) || (a->o_sb | a->o_ss) % 4 != 0) return MRAG_EINVAL;
-  if (a->resid && ((uintptr_t)a->resid & 7)) return MRAG_EINVAL;
-  // the scalar-base LDS-DMA path folds a tile's per-lane K / V offsets (up to 63 rows) into 32-bit unsigned byte offsets
-  if (a->k_ss < 0 || a->v_ss < 0 || a->k_ss > 0x1ffffff || a->v_ss > 0x1ffffff) return MRAG_ENOTSUP;
-  AttnP p{};
-  p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.V = (const bf16_t*)a->V;
-  p.O = (bf16_t*)a->O; p.resid = (const bf16_t*)a->resid; p.mask = a->mask;
-  p.bias = a->bias; p.bias_sh = a->bias_sh;
-  if (a->bias && (((uintptr_t)a->bias & 3) || a->bias_sh < 0)) return MRAG_EINVAL;
-  const bool masked = a->mask || a->bias;   // either one takes the 32x32x16 kernel's per-score path
-  p.q_sb = a->q_sb; p.q_ss = a->q_ss; p.q_sh = a->q_sh;
-  p.k_sb = a->k_sb; p.k_ss = a->k_ss; p.k_sh = a->k_sh;
-  p.v_sb = a->v_sb; p.v_ss = a->v_ss; p.v_sh = a->v_sh;
-  p.o_sb = a->o_sb; p.o_ss = a->o_ss;
-  p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Skv = a->Skv; p.kv_div = a->kv_batch_div;
-  p.qscale = a->q_prescaled ? 1.0f : a->scale * 1.4426950408889634f;
-  p.out_scale = a->out_scale;
-  hipStream_t s = (hipStream_t)stream;
-  if (a->Sq <= 16 && a->Skv <= 16 && !masked && !a->resid && !(a->tuning & MRAG_ATTN_TUNE_NO_TINY)) {   // temporal attention of the UNets
-    const long long pairs = (long long)a->B * a->H;
-    long long blocks = (pairs + 3) / 4;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    MRAG_LAUNCH(attn_tiny_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
-    MRAG_LAUNCH_CHECK();
-    MRAG_COUNT(MRAG_K_ATTN_TINY);
-    return MRAG_OK;
-  }
-  if (a->Sq > 128 && a->Skv <= KVB) return launch_attn<8, true>(s, p);
-  const bool legacy = (a->tuning & MRAG_ATTN_TUNE_LEGACY) != 0;
-  const bool may_split = a->Sq > 128 && !masked && a->workspace;   // key-split tail for the ragged last query tile (plan_kv_split)
-  if (may_split && ((uintptr_t)a->workspace & 15) != 0) return MRAG_EINVAL;
-  if (a->Sq > 128 && !masked && !legacy) {        // long unmasked sequences: the 16x16x32 family (attn16.hip), 192-row workgroups
-    SplitPlan pl;
-    bool split = false;
-    if (may_split) {
-      pl = mrag_plan_kv_split(a->B, a->H, a->Sq, a->Skv, mrag_attn16_rows(mrag_attn16_qb(a->Sq)), mrag_attn16_slots(mrag_attn16_qb(a->Sq)));
-      split = pl.splits > 1 && a->workspace_bytes >= (int64_t)pl.bytes;
-    }
-    const int rc = mrag_launch_attn16(s, p, split ? &pl : nullptr, a->workspace, mrag_attn16_qb(a->Sq));
-    if (rc != MRAG_ENOTSUP) return rc;
-  }
-  if (may_split) {
-    const SplitPlan pl = mrag_plan_kv_split(a->B, a->H, a->Sq, a->Skv, 256, 512);
-    if (pl.splits > 1 && a->workspace_bytes >= (int64_t)pl.bytes) return launch_attn_split(s, p, pl, a->workspace);
-  }
-  if (a->Sq > 128) return launch_attn<8>(s, p);
-  if (a->Sq > 32) return launch_attn<2>(s, p);
-  return launch_attn<1>(s, p);
+MRAG_FAMILY_LAUNCHER mrag_launch_attn_flash(hipStream_t s, const AttnP& p, int nw, bool short_kv, const SplitPlan* pl, void* workspace) {
+  if (pl) return launch_attn_split(s, p, *pl, workspace);
+  if (short_kv) return launch_attn<8, true>(s, p);
+  return nw == 8 ? launch_attn<8>(s, p) : (nw == 2 ? launch_attn<2>(s, p) : launch_attn<1>(s, p));
 }

@@ -27,7 +27,6 @@
 // Precision: e4m3 carries 3 mantissa bits: expect ~3-6 % relative Frobenius error against fp32 attention (tests state the tolerance);
 // this path is opt-in (config #5) and never used for the bf16 headline workload.
 #include "attn_common.h"
-#include "../../include/mrag_hip.h"
 
 namespace {
 
@@ -351,28 +350,16 @@ namespace {
 
 // both entry points: `joint` lifts mrag_attn_fwd_fp8's two refusals (Skv % 128, q_prescaled) and adds none of its own
 int fwd_fp8(void* stream, const mrag_attn_args* a, bool joint) {
-  if (!a || !a->Q || !a->K || !a->V || !a->O || !a->workspace) return MRAG_EINVAL;
-  if (a->B <= 0 || a->H <= 0 || a->Sq <= 0 || a->Skv <= 0) return MRAG_EINVAL;
+  if (!attn_args_present(a) || !a->workspace) return MRAG_EINVAL;
   if (a->mask || a->kv_batch_div != 1 || a->Skv < 4 * KT) return MRAG_ENOTSUP;
   if (joint ? a->bias != nullptr : (a->Skv % KT != 0 || a->q_prescaled)) return MRAG_ENOTSUP;
   const int skvp = pad_keys(a->Skv);                         // == Skv on the old entry point
   const bool ragged = skvp != a->Skv;
-  if (((uintptr_t)a->Q | (uintptr_t)a->K | (uintptr_t)a->V | (uintptr_t)a->workspace) & 15) return MRAG_EINVAL;
-  if ((a->q_sb | a->q_ss | a->q_sh | a->k_sb | a->k_ss | a->k_sh | a->v_sb | a->v_ss | a->v_sh) % 8 != 0) return MRAG_EINVAL;
-  if (((uintptr_t)a->O & 7) || (a->o_sb | a->o_ss) % 4 != 0 || (a->resid && ((uintptr_t)a->resid & 7))) return MRAG_EINVAL;
+  if (!attn_args_aligned(a, 8) || ((uintptr_t)a->workspace & 15)) return MRAG_EINVAL;
   if (a->workspace_bytes < mrag_attn_fp8_workspace_bytes(a->B, a->H, a->Sq, skvp)) return MRAG_EINVAL;
   Fp8P fp{};
   AttnP& p = fp.a;
-  p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.V = (const bf16_t*)a->V;
-  p.O = (bf16_t*)a->O; p.resid = (const bf16_t*)a->resid;
-  p.q_sb = a->q_sb; p.q_ss = a->q_ss; p.q_sh = a->q_sh;
-  p.k_sb = a->k_sb; p.k_ss = a->k_ss; p.k_sh = a->k_sh;
-  p.v_sb = a->v_sb; p.v_ss = a->v_ss; p.v_sh = a->v_sh;
-  p.o_sb = a->o_sb; p.o_ss = a->o_ss;
-  p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Skv = a->Skv; p.kv_div = 1;
-  // q_prescaled: Q already carries scale * log2 e (the QKV GEMM's q_premul) -- the quantiser's multiplier and the exponent y both use 1
-  p.qscale = a->q_prescaled ? 1.0f : a->scale * 1.4426950408889634f;
-  p.out_scale = a->out_scale;
+  attn_fill(p, a);   // (kv_div = 1, no mask, no bias; q_prescaled: the quantiser's multiplier and the exponent y both use 1)
   p.n_qtiles = (a->Sq + 255) / 256;
   const size_t bh = (size_t)a->B * a->H;
   char* ws = (char*)a->workspace;

@@ -4,10 +4,7 @@
 //   one workgroup per (batch, head): K and V of the head are staged in LDS as bf16 (Skv * D * 4 bytes <= 128 KB); a thread owns query rows tid, tid + 256, ...
 //   with the row's Q and its output accumulator in registers, walks the keys in blocks of 16 (scores -> block max -> one rescale of the accumulator -> exp2 -> P V).
 //   Every lane reads the same K / V element at the same time: LDS broadcasts, no bank conflicts.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "../../include/mrag_hip.h"
-#include "common.h"
+#include "attn_common.h"
 
 namespace {
 
@@ -124,16 +121,12 @@ int launch_small(hipStream_t s, const SmallP& p) {
 }  // namespace
 
 extern "C" int mrag_attn_small_bf16(void* stream, const mrag_attn_args* a, int32_t head_dim) {
-  if (!a || !a->Q || !a->K || !a->V || !a->O || a->B <= 0 || a->H <= 0 || a->Sq <= 0 || a->Skv <= 0) return MRAG_EINVAL;
+  if (!attn_args_present(a)) return MRAG_EINVAL;
   if (a->mask || a->bias || a->resid || a->kv_batch_div != 1 || a->q_prescaled) return MRAG_ENOTSUP;
-  if (((uintptr_t)a->Q | (uintptr_t)a->K | (uintptr_t)a->V | (uintptr_t)a->O) & 15) return MRAG_EINVAL;
-  if ((a->q_sb | a->q_ss | a->q_sh | a->k_sb | a->k_ss | a->k_sh | a->v_sb | a->v_ss | a->v_sh | a->o_sb | a->o_ss) % 8 != 0) return MRAG_EINVAL;
+  if (!attn_args_aligned(a, 16)) return MRAG_EINVAL;   // 16-byte stores
   SmallP p;
-  p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.V = (const bf16_t*)a->V; p.O = (bf16_t*)a->O;
-  p.q_sb = a->q_sb; p.q_ss = a->q_ss; p.q_sh = a->q_sh; p.k_sb = a->k_sb; p.k_ss = a->k_ss; p.k_sh = a->k_sh;
-  p.v_sb = a->v_sb; p.v_ss = a->v_ss; p.v_sh = a->v_sh; p.o_sb = a->o_sb; p.o_ss = a->o_ss;
-  p.B = a->B; p.H = a->H; p.Sq = a->Sq; p.Skv = a->Skv;
-  p.qscale = a->scale * 1.4426950408889634f;
+  attn_fill_views(p, a);
+  p.qscale = a->scale * kLog2e;
   hipStream_t s = (hipStream_t)stream;
   switch (head_dim) {
     case 32: return launch_small<32>(s, p);

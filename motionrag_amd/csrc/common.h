@@ -175,3 +175,11 @@ inline int launch_dyn_lds(void (*kernel)(P), dim3 grid, dim3 block, size_t lds_b
 // are part of every kernel's mangled name), and a C++ function whose signature names such a type is local to its unit: C linkage is the form that crosses
 // units.  Hidden: none of them belongs to the library's ABI.
 #define MRAG_FAMILY_LAUNCHER extern "C" __attribute__((visibility("hidden"))) int
+
+// A kernel that is not in the unnamed namespace (its name in the code object stays what it is): keeps its host-side handle and launch stub out of the
+// library's dynamic symbols.  Host pass only: in the code object the kernel's symbol is what the runtime looks up by name.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MRAG_KERNEL_HOST_HIDDEN
+#else
+#define MRAG_KERNEL_HOST_HIDDEN __attribute__((visibility("hidden")))
+#endif

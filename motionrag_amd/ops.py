@@ -245,6 +245,17 @@ def fp8_joint_attention_supported(Sq: int, Skv: int, kv_batch_div: int = 1, mask
     return mask is None and kv_batch_div == 1 and Skv >= 512 and Sq >= 1
 
 
+def _attention_views(q, k, v, out) -> AttnArgs:
+    """a mrag_attn_args block with the pointers and strides of q / k / v [B, S, H, D] and out [B, Sq, H * D]"""
+    a = AttnArgs()
+    a.Q, a.K, a.V, a.O = _p(q), _p(k), _p(v), _p(out)
+    a.q_sb, a.q_ss, a.q_sh = q.stride(0), q.stride(1), q.stride(2)
+    a.k_sb, a.k_ss, a.k_sh = k.stride(0), k.stride(1), k.stride(2)
+    a.v_sb, a.v_ss, a.v_sh = v.stride(0), v.stride(1), v.stride(2)
+    a.o_sb, a.o_ss = out.stride(0), out.stride(1)
+    return a
+
+
 def _attention_args(q, k, v, out, resid, mask, kv_batch_div, scale, out_scale, q_prescaled, bias, fp8=False):
     """the checks and the mrag_attn_args block every attention entry point shares -> (args, out, mask as the kernels read it); `fp8`: a path that takes no bias"""
     for n, t in (("q", q), ("k", k), ("v", v)):
@@ -257,14 +268,9 @@ def _attention_args(q, k, v, out, resid, mask, kv_batch_div, scale, out_scale, q
         raise ValueError("kv batch * kv_batch_div must equal q batch")
     if out is None:
         out = torch.empty(B, Sq, H * 64, dtype=torch.bfloat16, device=q.device)
-    a = AttnArgs()
-    a.Q, a.K, a.V, a.O = _p(q), _p(k), _p(v), _p(out)
-    a.q_sb, a.q_ss, a.q_sh = q.stride(0), q.stride(1), q.stride(2)
-    a.k_sb, a.k_ss, a.k_sh = k.stride(0), k.stride(1), k.stride(2)
-    a.v_sb, a.v_ss, a.v_sh = v.stride(0), v.stride(1), v.stride(2)
     if out.stride(-1) != 1:
         raise ValueError("out must have a contiguous last dim")
-    a.o_sb, a.o_ss = out.stride(0), out.stride(1)
+    a = _attention_views(q, k, v, out)
     if resid is not None:
         _dev(resid, name="resid")
         if resid.stride() != out.stride():
@@ -293,10 +299,8 @@ def _attention_args(q, k, v, out, resid, mask, kv_batch_div, scale, out_scale, q
     return a, out, mask
 
 
-def _fp8_attention_launch(a: AttnArgs, device, need: int, entry: str, label: str) -> None:
-    """one of the two fp8 entry points on the "fp8" workspace (grow-only, per device and stream: no host synchronisation, graph-capturable once grown)"""
-    ws = _attn_workspace(device, need, "fp8")
-    a.workspace, a.workspace_bytes = _p(ws), ws.numel()
+def _attention_launch(a: AttnArgs, entry: str, label: str) -> None:
+    """call one head_dim-64 entry point; bench.py's roofline leg (KERNEL_TIMING): HIP events on the launch stream around each big launch"""
     timed = KERNEL_TIMING is not None and a.Skv >= 1024
     if timed:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -305,6 +309,13 @@ def _fp8_attention_launch(a: AttnArgs, device, need: int, entry: str, label: str
     if timed:
         e1.record()
         KERNEL_TIMING.append((label, 4.0 * a.B * a.H * a.Sq * a.Skv * 64, e0, e1))
+
+
+def _fp8_attention_launch(a: AttnArgs, device, need: int, entry: str, label: str) -> None:
+    """one of the two fp8 entry points on the "fp8" workspace (grow-only, per device and stream: no host synchronisation, graph-capturable once grown)"""
+    ws = _attn_workspace(device, need, "fp8")
+    a.workspace, a.workspace_bytes = _p(ws), ws.numel()
+    _attention_launch(a, entry, label)
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, out: Optional[torch.Tensor] = None,
@@ -329,14 +340,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, out: Optiona
         if need > 0:
             ws = _attn_workspace(q.device, need)
             a.workspace, a.workspace_bytes = _p(ws), ws.numel()
-    timed = KERNEL_TIMING is not None and Skv >= 1024
-    if timed:  # bench.py's roofline leg: HIP events on the launch stream around this one kernel
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(_lib.lib().mrag_attn_fwd_bf16(_stream(), ctypes.byref(a)), "mrag_attn_fwd_bf16")
-    if timed:
-        e1.record()
-        KERNEL_TIMING.append(("attn_fwd", 4.0 * B * H * Sq * Skv * 64, e0, e1))
+    _attention_launch(a, "mrag_attn_fwd_bf16", "attn_fwd")
     return out
 
 
@@ -366,12 +370,7 @@ def attention_small(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, scale:
     B, Sq, H, D = q.shape
     if out is None:
         out = torch.empty(B, Sq, H * D, dtype=torch.bfloat16, device=q.device)
-    a = AttnArgs()
-    a.Q, a.K, a.V, a.O = _p(q), _p(k), _p(v), _p(out)
-    a.q_sb, a.q_ss, a.q_sh = q.stride(0), q.stride(1), q.stride(2)
-    a.k_sb, a.k_ss, a.k_sh = k.stride(0), k.stride(1), k.stride(2)
-    a.v_sb, a.v_ss, a.v_sh = v.stride(0), v.stride(1), v.stride(2)
-    a.o_sb, a.o_ss = out.stride(0), out.stride(1)
+    a = _attention_views(q, k, v, out)
     a.B, a.H, a.Sq, a.Skv, a.kv_batch_div = B, H, Sq, k.shape[1], 1
     a.scale, a.out_scale = (D ** -0.5) if scale is None else scale, 1.0
     check(_lib.lib().mrag_attn_small_bf16(_stream(), ctypes.byref(a), D), "mrag_attn_small_bf16")

@@ -476,7 +476,7 @@ def test_attention_large_sequence_properties(hip):
 
 def test_attention_key_split_tail(hip):
     """long launches hand the ragged last query tile (Sq % 192 rows per head in attn16.hip, Sq % 256 in attn_flash.hip) to short key-chunk
-    workgroups + a merge kernel (plan_kv_split): the tail rows and a sample of the others equal the fp32 reference, with a fused residual,
+    workgroups + a merge kernel (attn_bf16.hip: mrag_plan_kv_split, attn_combine_kernel): the tail rows and a sample of the others equal the fp32 reference, with a fused residual,
     and agree with the unsplit kernel to a bf16 ulp or two -- for both kernel families"""
     from motionrag_amd import ops, _lib
     g = torch.Generator().manual_seed(9)
@@ -558,6 +558,75 @@ def test_attention_baseline_shape_split_tail_properties(hip):
     for h in (0, 23, 47):
         want = sdpa_ref(q[:, rows, h:h + 1], k[:, :, h:h + 1], v[:, :, h:h + 1])
         close(out[:, rows.to(DEV), h * 64:(h + 1) * 64], want, scale=0.05, rtol=3e-2, atol_frac=5e-2)
+
+
+def test_attention_routes(hip):
+    """which kernel family every branch of mrag_attn_fwd_bf16's dispatch takes, at the smallest shapes on each side of it (one call per row, the exact launch
+    counts), with the values against the fp32 reference; the rows at 32 / 33 and 128 / 129 queries also cross the wave counts of the 32x32x16 launcher, which
+    the counters do not show.  mrag_attn_small_bf16 and mrag_ip_attn_folded_bf16 close the table.  (The key-split routes need long sequences:
+    test_attention_key_split_tail.)"""
+    from motionrag_amd import ops
+    g = torch.Generator().manual_seed(11)
+    B, H = 1, 2
+    routes = [  # Sq, Skv, extra, tuning, expected counts
+        (16, 16, None, 0, {"ATTN_TINY": 1}),
+        (16, 16, "resid", 0, {"ATTN_FLASH": 1}),
+        (16, 16, None, ops.ATTN_TUNE_NO_TINY, {"ATTN_FLASH": 1}),
+        (32, 65, None, 0, {"ATTN_FLASH": 1}),
+        (33, 65, None, 0, {"ATTN_FLASH": 1}),
+        (128, 65, None, 0, {"ATTN_FLASH": 1}),
+        (129, 64, None, 0, {"ATTN_FLASH": 1}),
+        (129, 65, None, 0, {"ATTN_FLASH": 1}),                 # the attn16 launcher refuses fewer than 256 keys: the call falls through
+        (129, 256, None, 0, {"ATTN16": 1}),
+        (129, 256, "mask", 0, {"ATTN_FLASH": 1}),
+        (129, 256, "bias", 0, {"ATTN_FLASH": 1}),
+        (129, 256, None, ops.ATTN_TUNE_LEGACY, {"ATTN_FLASH": 1}),
+    ]
+    for Sq, Skv, extra, tuning, counts in routes:
+        q = bf(torch.randn(B, Sq, H, 64, generator=g))
+        k, v = (bf(torch.randn(B, Skv, H, 64, generator=g)) for _ in range(2))
+        kw, want = {}, None
+        if extra == "resid":
+            resid = bf(torch.randn(B, Sq, H * 64, generator=g))
+            kw["resid"] = resid.to(DEV)
+            want = resid.float() + sdpa_ref(q, k, v)
+        elif extra == "mask":
+            mask = torch.rand(Sq, Skv, generator=g) < 0.5
+            mask[:, 0] = False                                  # the first key open in every row
+            kw["mask"] = mask.to(DEV)
+            want = sdpa_ref(q, k, v, mask=mask)
+        elif extra == "bias":
+            bias = torch.randn(H, Sq, Skv, generator=g)
+            kw["bias"] = bias.to(DEV)
+            qf, kf, vf = (t.float().permute(0, 2, 1, 3) for t in (q, k, v))
+            want = (torch.softmax(qf @ kf.transpose(-1, -2) / 8.0 + bias, dim=-1) @ vf).permute(0, 2, 1, 3).reshape(B, Sq, -1)
+        else:
+            want = sdpa_ref(q, k, v)
+        ops.TUNING["attn"] = tuning
+        try:
+            with ops.dispatched() as d:
+                got = ops.attention(q.to(DEV), k.to(DEV), v.to(DEV), **kw)
+        finally:
+            ops.TUNING["attn"] = 0
+        assert d.counts == counts, (Sq, Skv, extra, tuning, d.counts)
+        close(got, want, scale=1.0 if extra == "resid" else 0.3)
+    # head dim 32, 17 x 17
+    q, k, v = (bf(torch.randn(B, 17, H, 32, generator=g)) for _ in range(3))
+    with ops.dispatched() as d:
+        got = ops.attention_small(q.to(DEV), k.to(DEV), v.to(DEV))
+    assert d.counts == {"ATTN_SMALL": 1}, d.counts
+    qf, kf, vf = (t.float().permute(0, 2, 1, 3) for t in (q, k, v))
+    close(got, (torch.softmax(qf @ kf.transpose(-1, -2) * 32 ** -0.5, dim=-1) @ vf).permute(0, 2, 1, 3).reshape(B, 17, -1), scale=0.3)
+    # the folded motion-adapter branch at its smallest legal shape
+    S, keys = 64, 25
+    sc = bf(torch.randn(B, S, H, 32, generator=g) * 3)
+    vi = bf(torch.randn(B, keys, H * 64, generator=g))
+    hid = bf(torch.randn(B, S, H * 64, generator=g))
+    with ops.dispatched() as d:
+        got = ops.ip_attn_folded_(sc.view(B, S, H * 32).to(DEV), vi.to(DEV), hid.to(DEV).clone(), H, keys, key_stride=32)
+    assert d.counts == {"IP_ATTN_FOLDED": 1}, d.counts
+    p = torch.softmax(sc.float()[..., :keys] * 0.125, dim=-1)
+    close(got, hid.float() + torch.einsum("bshk,bkhd->bshd", p, vi.float().view(B, keys, H, 64)).reshape(B, S, H * 64), scale=1.0)
 
 
 # ---------------------------------------------------------------------------------------------- norms
@@ -921,7 +990,7 @@ def test_gemm_geglu_epilogue(hip, M, inner, K):
 
 @pytest.mark.parametrize("B,H,Sq,Skv,kvdiv", [(37, 5, 16, 16, 1), (100, 3, 14, 14, 1), (9, 2, 1, 16, 1), (12, 4, 16, 5, 3), (1000, 5, 16, 16, 1)])
 def test_attention_tiny_sequences(hip, B, H, Sq, Skv, kvdiv):
-    """the per-wave kernel for <= 16 x 16 attention (UNet temporal attention): contiguous layout, the strided (b hw) t c view the temporal
+    """the per-wave kernel for <= 16 x 16 attention (attn_tiny.hip; UNet temporal attention): contiguous layout, the strided (b hw) t c view the temporal
     transformers hand over, kv batch repeat, out_scale, pre-scaled Q -- and agreement with the 64-key-tile kernel on the same inputs"""
     from motionrag_amd import ops
     g = torch.Generator().manual_seed(B + Sq)
