@@ -367,6 +367,41 @@ int mrag_attn_fwd_bf16(void* stream, const mrag_attn_args* args);
  * instead of B*H full-length stragglers; 0 when the shape has no such tail.  */
 int64_t mrag_attn_workspace_bytes(int32_t B, int32_t H, int32_t Sq, int32_t Skv);
 
+/* Packed variable-length attention (the `cu_seqlens` form), head_dim 64, bf16: B sequences of their own lengths share one packed row matrix, and
+ * sequence i, rows [s_i, e_i) = [cu_seqlens[i], cu_seqlens[i + 1]), attends to itself only:
+ *   O[s_i:e_i] = softmax(scale * Q[s_i:e_i] K[s_i:e_i]^T) V[s_i:e_i]            per head.
+ * Stands behind the attention of the retrieval row's text encoder when captions of different token counts are embedded in one forward pass: the
+ * LanceDB table's embedding function (tools/build_rag_database.py:16-33: every caption when a database is built) and the query embedding
+ * (src/data/rag.py:13-15).  The library that model would call pads and masks the batch; here the valid tokens are packed and no key of a neighbouring
+ * sequence, and no padding, is ever read.
+ * Rows of O at or beyond cu_seqlens[B] are not written (the caller may over-allocate); a zero-length sequence writes nothing.  max_seqlen sizes the
+ * grid -- ceil(max_seqlen / 64) x H x B workgroups of 64 query rows; one whose first row is at or beyond its sequence's length returns at once -- and is a
+ * HOST integer: the launch reads no device memory on the host, does not synchronise and can be captured in a HIP graph.  Rows of a sequence beyond
+ * max_seqlen are not computed.  A workgroup whose cu_seqlens pair is not as required below returns without reading or writing a row.
+ * No mask, bias, residual, kv_batch_div or pre-scaled Q.  Same tile arithmetic as mrag_attn_fwd_bf16's 32x32x16 family (attn_flash_tile.h).
+ * MRAG_EINVAL: a null args / Q / K / V / O / cu_seqlens; B, H or max_seqlen <= 0; max_seqlen > total_rows; Q / K / V not 16-byte aligned or a stride of
+ * theirs not a multiple of 8 elements; O not 8-byte aligned or o_ss not a multiple of 4; cu_seqlens not 4-byte aligned.  Then MRAG_ENOTSUP: k_ss or v_ss
+ * outside [0, 0x1ffffff] (the 32-bit byte offsets of the LDS-DMA path, as mrag_attn_fwd_bf16), H or B above 65 535 (grid dimensions).  Every check
+ * returns before any launch.                                                                                                                        */
+typedef struct mrag_attn_varlen_args {
+  const void* Q;   /* element (row r, head h, d) at Q + r*q_ss + h*q_sh + d: views of one fused [T, 3*H*64] QKV buffer work */
+  const void* K;
+  const void* V;
+  void* O;         /* element (r, h, d) at O + r*o_ss + h*64 + d */
+  const int32_t* cu_seqlens;   /* DEVICE int32 [B + 1], non-decreasing, cu_seqlens[0] = 0, cu_seqlens[B] = total_rows */
+  int64_t q_ss, q_sh;
+  int64_t k_ss, k_sh;
+  int64_t v_ss, v_sh;
+  int64_t o_ss;
+  int32_t B, H, total_rows;
+  int32_t max_seqlen;          /* host integer >= the longest sequence */
+  float scale;                 /* softmax scale */
+} mrag_attn_varlen_args;
+int mrag_attn_varlen_fwd_bf16(void* stream, const mrag_attn_varlen_args* args);
+/* host-side relaxed launch counter in the form of mrag_ff_fused_launch_counts: ONE slot, the launches of mrag_attn_varlen_fwd_bf16 (not its refusals).
+ * Copies min(n, 1) slots into out_host (HOST memory), returns 1; answers without a device.  enum mrag_kernel_id keeps its enumerators.              */
+int mrag_attn_varlen_launch_counts(uint64_t* out_host, int32_t n);
+
 /* fp8 (OCP e4m3) attention path -- BASELINE config "DynamiCrafter-1024 UNet 16x576x1024 + CAMA, fp8 MFMA attention path": the
  * spatial self-attention SDPA of the UNets (lvdm/modules/attention.py:189; diffusers BasicTransformerBlock.attn1 of the SVD UNet).
  * Same argument struct and result as mrag_attn_fwd_bf16 (bf16 Q / K / V views in, bf16 O out, fused residual); inside: per-(batch, head)

@@ -18,12 +18,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libmrag_hip.so")
 # compiled in this order, at most MAX_COMPILERS at a time: the long units first, so that none of them starts late behind the short ones
-SOURCES = ["gemm_tiled.hip", "gemm_w4.hip", "topk_scan.hip", "gemm_conv.hip", "attn16.hip", "topk_dense.hip", "topk_mfma.hip", "attn_flash.hip", "gemm_skinny.hip", "gemm_fp8.hip", "ff_fused.hip", "conv_fp8.hip", "api.hip", "gemm_bf16.hip", "gemm_k320.hip", "attn_fp8.hip",
+SOURCES = ["gemm_tiled.hip", "gemm_w4.hip", "topk_scan.hip", "gemm_conv.hip", "attn16.hip", "topk_dense.hip", "topk_mfma.hip", "attn_flash.hip", "attn_varlen.hip", "gemm_skinny.hip", "gemm_fp8.hip", "ff_fused.hip", "conv_fp8.hip", "api.hip", "gemm_bf16.hip", "gemm_k320.hip", "attn_fp8.hip",
            "comm.hip", "norm.hip", "pointwise.hip", "preprocess.hip", "unet_ops.hip", "cama_seq.hip", "attn_ip_folded.hip", "attn_bf16.hip", "attn_small.hip", "attn_tiny.hip", "topk.hip", "probe.hip"]
 MAX_COMPILERS = 16
 ABI_VERSION = 11
 # per-file flags: the SLP vectoriser packs the softmax row-sum adds into v_pk_add_f32 + shuffles (slower beside MFMAs)
-EXTRA_FLAGS = {f: ["-fno-slp-vectorize"] for f in ("attn_flash.hip", "attn_tiny.hip", "attn_ip_folded.hip", "attn_bf16.hip", "attn16.hip", "attn_fp8.hip")}
+EXTRA_FLAGS = {f: ["-fno-slp-vectorize"] for f in ("attn_flash.hip", "attn_varlen.hip", "attn_tiny.hip", "attn_ip_folded.hip", "attn_bf16.hip", "attn16.hip", "attn_fp8.hip")}
 
 # every symbol include/mrag_hip.h declares (tests check the .so exports all of them)
 SYMBOLS = [
@@ -39,6 +39,7 @@ SYMBOLS = [
     "mrag_layernorm_e4m3", "mrag_gemm_fp8_k64", "mrag_gemm_fp8_k64_launch_counts",
     "mrag_groupnorm_split_workspace_bytes", "mrag_groupnorm_partial_bf16", "mrag_groupnorm_apply_stats_bf16", "mrag_swap_outer_bf16",
     "mrag_ff_fused_bf16", "mrag_ff_fused_supported", "mrag_ff_fused_launch_counts",
+    "mrag_attn_varlen_fwd_bf16", "mrag_attn_varlen_launch_counts",
 ]
 
 
@@ -95,6 +96,14 @@ class AttnArgs(Structure):
         ("scale", c_float), ("out_scale", c_float), ("q_prescaled", c_int32),
         ("workspace", c_void_p), ("workspace_bytes", c_int64), ("tuning", c_int32),
         ("bias", c_void_p), ("bias_sh", c_int64),
+    ]
+
+
+class AttnVarlenArgs(Structure):
+    _fields_ = [
+        ("Q", c_void_p), ("K", c_void_p), ("V", c_void_p), ("O", c_void_p), ("cu_seqlens", c_void_p),
+        ("q_ss", c_int64), ("q_sh", c_int64), ("k_ss", c_int64), ("k_sh", c_int64), ("v_ss", c_int64), ("v_sh", c_int64), ("o_ss", c_int64),
+        ("B", c_int32), ("H", c_int32), ("total_rows", c_int32), ("max_seqlen", c_int32), ("scale", c_float),
     ]
 
 
@@ -325,6 +334,8 @@ def lib() -> ctypes.CDLL:
     L.mrag_attn_joint_fp8_workspace_bytes.restype = c_int64
     L.mrag_attn_joint_fwd_fp8.argtypes = [c_void_p, POINTER(AttnArgs)]
     L.mrag_attn_small_bf16.argtypes = [c_void_p, POINTER(AttnArgs), c_int32]
+    L.mrag_attn_varlen_fwd_bf16.argtypes = [c_void_p, POINTER(AttnVarlenArgs)]
+    L.mrag_attn_varlen_launch_counts.argtypes = [c_void_p, c_int32]
     L.mrag_comm_unique_id.argtypes = [c_void_p]
     L.mrag_comm_init.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]
     L.mrag_comm_destroy.argtypes = [c_void_p]

@@ -2,7 +2,8 @@
 // key-split plan of long launches and the launchers that cross units.  One unit per kernel family:
 //   attn_bf16.hip       mrag_attn_fwd_bf16 (dispatch only), the key-split planner and the merge kernel of its partial results
 //   attn16.hip          16x16x32 family: long unmasked sequences (the joint attention)
-//   attn_flash.hip      32x32x16 family: short / masked / biased / cross-attention launches
+//   attn_flash.hip      32x32x16 family: short / masked / biased / cross-attention launches (its tile functions: attn_flash_tile.h)
+//   attn_varlen.hip     the same tile functions over packed variable-length sequences (mrag_attn_varlen_fwd_bf16; its own parameter block)
 //   attn_tiny.hip       one wavefront per (batch, head) for <= 16 x 16 (temporal attention of the UNets)
 //   attn_fp8.hip        e4m3 operands (mrag_attn_fwd_fp8, mrag_attn_joint_fwd_fp8)
 //   attn_small.hip      other head dims (mrag_attn_small_bf16; its own parameter block)

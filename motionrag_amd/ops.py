@@ -12,7 +12,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, FfFusedArgs, GemmArgs, GemmFp8Args, LnArgs, QkNormRopeArgs, check
+from ._lib import AttnArgs, AttnVarlenArgs, FfFusedArgs, GemmArgs, GemmFp8Args, LnArgs, QkNormRopeArgs, check
 
 EPI_NONE, EPI_GELU_TANH, EPI_GELU_ERF, EPI_RESID, EPI_GATE_RESID, EPI_SILU, EPI_GEGLU, EPI_QKNORM_ROPE = range(8)
 LOG2E = 1.4426950408889634
@@ -341,6 +341,54 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, out: Optiona
             ws = _attn_workspace(q.device, need)
             a.workspace, a.workspace_bytes = _p(ws), ws.numel()
     _attention_launch(a, "mrag_attn_fwd_bf16", "attn_fwd")
+    return out
+
+
+def attn_varlen_launch_counts() -> int:
+    """launches of mrag_attn_varlen_fwd_bf16 so far (mrag_attn_varlen_launch_counts; refused calls do not count)"""
+    buf = (ctypes.c_uint64 * 1)()
+    _lib.lib().mrag_attn_varlen_launch_counts(buf, 1)
+    return int(buf[0])
+
+
+def attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: int, *, out: Optional[torch.Tensor] = None,
+                     scale: Optional[float] = None) -> torch.Tensor:
+    """packed variable-length attention for head_dim 64 (mrag_attn_varlen_fwd_bf16): sequence i is rows [cu_seqlens[i], cu_seqlens[i + 1]) and attends to itself only.
+
+    q, k, v [T, H, 64] (any strides with the last dim contiguous, e.g. views of a fused [T, 3 * H * 64] QKV buffer); cu_seqlens int32 [B + 1] on the device,
+    non-decreasing from 0 to T; max_seqlen: a Python int >= the longest sequence (it sizes the grid; nothing is read back from the device).  out [>= T, H * 64]
+    with a contiguous last dim: rows at or beyond cu_seqlens[-1] are left as they are.
+    """
+    for n, t in (("q", q), ("k", k), ("v", v)):
+        _dev(t, name=n)
+        if t.dim() != 3 or t.shape[-1] != 64 or t.stride(-1) != 1:
+            raise ValueError(f"{n}: expected [T, H, 64] with contiguous head dim, got {tuple(t.shape)}")
+    T, H, _ = q.shape
+    if k.shape != q.shape or v.shape != q.shape:
+        raise ValueError(f"q, k and v must share one [T, H, 64] shape, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    _dev(cu_seqlens, torch.int32, "cu_seqlens")
+    if cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2 or not cu_seqlens.is_contiguous():
+        raise ValueError(f"cu_seqlens: expected a contiguous int32 [B + 1], got {tuple(cu_seqlens.shape)}")
+    if k.device != q.device or v.device != q.device or cu_seqlens.device != q.device:
+        raise ValueError("q, k, v and cu_seqlens must be on one device")
+    if isinstance(max_seqlen, bool) or not isinstance(max_seqlen, int):
+        raise TypeError(f"max_seqlen: expected a Python int (a host value: the launch reads nothing back), got {type(max_seqlen).__name__}")
+    if not 0 < max_seqlen <= T:
+        raise ValueError(f"max_seqlen = {max_seqlen} outside [1, T = {T}]")
+    if out is None:
+        out = torch.empty(T, H * 64, dtype=torch.bfloat16, device=q.device)
+    _dev(out, name="out")
+    if out.dim() != 2 or out.shape[0] < T or out.shape[1] != H * 64 or out.stride(-1) != 1 or out.device != q.device:
+        raise ValueError(f"out: expected [>= {T}, {H * 64}] with a contiguous last dim on q's device, got {tuple(out.shape)}")
+    a = AttnVarlenArgs()
+    a.Q, a.K, a.V, a.O, a.cu_seqlens = _p(q), _p(k), _p(v), _p(out), _p(cu_seqlens)
+    a.q_ss, a.q_sh = q.stride(0), q.stride(1)
+    a.k_ss, a.k_sh = k.stride(0), k.stride(1)
+    a.v_ss, a.v_sh = v.stride(0), v.stride(1)
+    a.o_ss = out.stride(0)
+    a.B, a.H, a.total_rows, a.max_seqlen = cu_seqlens.numel() - 1, H, T, max_seqlen
+    a.scale = (64 ** -0.5) if scale is None else scale
+    check(_lib.lib().mrag_attn_varlen_fwd_bf16(_stream(), ctypes.byref(a)), "mrag_attn_varlen_fwd_bf16")
     return out
 
 

@@ -27,6 +27,8 @@ if __name__ == "__main__":
     ap.add_argument("--ref_video_num", type=int, default=9)
     ap.add_argument("--gte_dir", type=str, default=None, help="local snapshot of Alibaba-NLP/gte-base-en-v1.5 (model.safetensors + tokenizer files): captions are embedded by "
                     "motionrag_amd.text_embedder on the GPU, as the reference's LanceDB embedding function does (tools/build_rag_database.py:28-31); default: hash-seeded unit vectors")
+    ap.add_argument("--packed", action="store_true", help="with --gte_dir: captions of all lengths share a forward pass (SentenceEmbedder(packed=True): packed "
+                    "variable-length attention) instead of one pass per distinct token count")
     args = ap.parse_args()
 
     annotations = torch.load(args.annotations_path) if args.annotations_path else rag.synthetic_captions(args.n_synthetic)
@@ -48,7 +50,8 @@ if __name__ == "__main__":
         sd = safetensors.torch.load_file(os.path.join(args.gte_dir, "model.safetensors"))
         model.load_state_dict({k[len("new."):] if k.startswith("new.") else k: v for k, v in sd.items() if "position_ids" not in k and not k.startswith("pooler")}, strict=True)
         tok = AutoTokenizer.from_pretrained(args.gte_dir)
-        embedder = SentenceEmbedder(model.to("cuda", torch.bfloat16), lambda texts: tok(list(texts), truncation=True, max_length=8192)["input_ids"])
+        embedder = SentenceEmbedder(model.to("cuda", torch.bfloat16), lambda texts: tok(list(texts), truncation=True, max_length=8192)["input_ids"],
+                                    packed=args.packed)
         texts = [a[args.caption_name] or "" for a in annotations]
         emb = torch.cat([embedder.encode(texts[i:i + 4096]) for i in range(0, len(texts), 4096)]).cpu().numpy()
     else:
