@@ -9,10 +9,11 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
@@ -25,169 +26,102 @@ ABI_VERSION = 11
 # per-file flags: the SLP vectoriser packs the softmax row-sum adds into v_pk_add_f32 + shuffles (slower beside MFMAs)
 EXTRA_FLAGS = {f: ["-fno-slp-vectorize"] for f in ("attn_flash.hip", "attn_varlen.hip", "attn_tiny.hip", "attn_ip_folded.hip", "attn_bf16.hip", "attn16.hip", "attn_fp8.hip")}
 
-# every symbol include/mrag_hip.h declares (tests check the .so exports all of them)
-SYMBOLS = [
-    "mrag_abi_version", "mrag_target_arch", "mrag_source_hash", "mrag_dispatch_counts", "mrag_dispatch_name", "mrag_probe_mfma_flops", "mrag_probe_mfma_bf16", "mrag_probe_mfma_f32_flops", "mrag_probe_mfma_f32", "mrag_probe_stream_copy", "mrag_gemm_bf16", "mrag_gemm_workspace_bytes", "mrag_attn_fwd_bf16", "mrag_attn_workspace_bytes", "mrag_layernorm_bf16",
-    "mrag_qknorm_rope_bf16", "mrag_timestep_embedding_bf16", "mrag_silu_bf16", "mrag_add_rows_bf16", "mrag_add_bf16", "mrag_add_bcast_bf16", "mrag_axpby_bf16", "mrag_cfg_euler_step_bf16", "mrag_conv_bf16", "mrag_ip_attn_folded_bf16",
-    "mrag_patchify_bf16", "mrag_unpatchify_bf16", "mrag_cfg_ddim_step_bf16", "mrag_topk_workspace_bytes", "mrag_topk_workspace_bytes_k", "mrag_topk_f32", "mrag_topk_rerank_f32",
-    "mrag_groupnorm_workspace_bytes", "mrag_groupnorm_bf16", "mrag_im2col3x3_bf16", "mrag_unfold_t3_bf16", "mrag_geglu_bf16",
-    "mrag_ddim_v_step_f32", "mrag_ddim_v_rescale_workspace_bytes", "mrag_ddim_v_step_rescaled_f32", "mrag_weighted_sum_bf16", "mrag_attn_fp8_workspace_bytes", "mrag_attn_fwd_fp8", "mrag_attn_joint_fp8_workspace_bytes", "mrag_attn_joint_fwd_fp8",
-    "mrag_comm_unique_id", "mrag_comm_init", "mrag_comm_destroy", "mrag_allgather",
-    "mrag_resize_patchify_bf16", "mrag_assemble_tokens_bf16", "mrag_softmax_rows_bf16", "mrag_denormalize_u8", "mrag_attn_small_bf16", "mrag_blend_tile_bf16", "mrag_cfg_dpm_step_bf16",
-    "mrag_resampler_workspace_bytes", "mrag_resampler_fwd", "mrag_cama_encoder_workspace_bytes", "mrag_cama_encoder_fwd",
-    "mrag_quant_rows_e4m3", "mrag_gemm_fp8", "mrag_fp8_launch_counts", "mrag_conv_fp8", "mrag_conv_fp8_launch_counts",
-    "mrag_layernorm_e4m3", "mrag_gemm_fp8_k64", "mrag_gemm_fp8_k64_launch_counts",
-    "mrag_groupnorm_split_workspace_bytes", "mrag_groupnorm_partial_bf16", "mrag_groupnorm_apply_stats_bf16", "mrag_swap_outer_bf16",
-    "mrag_ff_fused_bf16", "mrag_ff_fused_supported", "mrag_ff_fused_launch_counts",
-    "mrag_attn_varlen_fwd_bf16", "mrag_attn_varlen_launch_counts",
-]
-
-
-# entry points whose result is not the int32 status code (their restype is set explicitly in lib())
-_NON_INT_RESULT = ("mrag_target_arch", "mrag_source_hash", "mrag_dispatch_name", "mrag_probe_mfma_flops", "mrag_probe_mfma_f32_flops", "mrag_gemm_workspace_bytes", "mrag_attn_workspace_bytes", "mrag_attn_fp8_workspace_bytes", "mrag_attn_joint_fp8_workspace_bytes", "mrag_topk_workspace_bytes", "mrag_topk_workspace_bytes_k", "mrag_groupnorm_workspace_bytes",
-                   "mrag_ddim_v_rescale_workspace_bytes", "mrag_resampler_workspace_bytes", "mrag_cama_encoder_workspace_bytes", "mrag_groupnorm_split_workspace_bytes")
-
 
 class HipLibraryMissing(RuntimeError):
     pass
 
 
-class GemmArgs(Structure):
-    _fields_ = [
-        ("A", c_void_p), ("W", c_void_p), ("bias", c_void_p), ("C", c_void_p), ("resid", c_void_p),
-        ("gate0", c_void_p), ("gate1", c_void_p),
-        ("M", c_int64), ("N", c_int64), ("K", c_int64),
-        ("lda", c_int64), ("ldw", c_int64), ("ldc", c_int64), ("ldr", c_int64),
-        ("rows_per_batch", c_int64), ("split", c_int64), ("gate_stride", c_int64),
-        ("epilogue", c_int32), ("rope_text_len", c_int32),
-        ("q_gamma", c_void_p), ("q_beta", c_void_p), ("k_gamma", c_void_p), ("k_beta", c_void_p), ("rope_cos", c_void_p), ("rope_sin", c_void_p),
-        ("qk_dmodel", c_int64), ("qk_eps", c_float), ("q_premul", c_float), ("qk_first", c_int32), ("tuning", c_int32), ("geglu_act", c_int32),
-        ("workspace", c_void_p), ("acc_scale", c_float), ("workspace_bytes", c_int64), ("w_batch_stride", c_int64),
-        ("a_ln_gamma", c_void_p), ("a_ln_beta", c_void_p), ("a_ln_eps", c_float), ("a_ln", c_int32),
-    ]
+# The C ABI is written down once, in include/mrag_hip.h; this table is the only hand-written part of its Python side.
+_SCALARS = {"int": c_int32, "int32_t": c_int32, "int64_t": c_int64, "uint64_t": c_uint64, "float": c_float}
+_POINTEES = set(_SCALARS) | {"void", "char", "uint8_t"}      # what a pointer that travels as c_void_p may point at
+_DECLARATOR = re.compile(r"(\**)\s*(\w+)\s*(?:\[\s*(\d+)\s*\])?")
 
 
-class GemmFp8Args(Structure):
-    _fields_ = [
-        ("A8", c_void_p), ("W8", c_void_p), ("a_exp", c_void_p), ("w_exp", c_void_p), ("bias", c_void_p), ("C", c_void_p), ("resid", c_void_p),
-        ("gate0", c_void_p), ("gate1", c_void_p),
-        ("M", c_int64), ("N", c_int64), ("K", c_int64),
-        ("lda", c_int64), ("ldw", c_int64), ("ldc", c_int64), ("ldr", c_int64),
-        ("rows_per_batch", c_int64), ("split", c_int64), ("gate_stride", c_int64),
-        ("epilogue", c_int32),
-    ]
+def _ctype(const, base, stars, structs, decl):
+    """the ctypes type of `[const] base` behind `stars` asterisks; anything outside the table raises, naming the declaration"""
+    if not stars and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 1 and const and base == "char":
+        return c_char_p
+    if stars == 1 and const and base in structs:
+        return POINTER(structs[base])
+    if stars == 2 and base == "void":
+        return POINTER(c_void_p)
+    if stars == 1 and base in _POINTEES:
+        return c_void_p
+    raise ValueError(f"mrag_hip.h: no ctypes mapping for the type of `{decl}`")
 
 
-class FfFusedArgs(Structure):
-    _fields_ = [
-        ("x", c_void_p), ("out", c_void_p), ("ln_gamma", c_void_p), ("ln_beta", c_void_p), ("w1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p),
-        ("rows", c_int64), ("C", c_int64), ("inner", c_int64), ("ldx", c_int64), ("ldo", c_int64), ("eps", c_float),
-    ]
+def _fields(body, structs):
+    """`const void *A, *W; int64_t M, N, K; float scale[4];` -> [(name, ctype)]: the asterisks and the array bound belong to each declarator"""
+    out = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        m = re.fullmatch(r"(const\s+)?(\w+)\b\s*(.*)", decl, re.S)
+        parts = [_DECLARATOR.fullmatch(p.strip()) for p in m.group(3).split(",")] if m else [None]
+        if not all(parts):
+            raise ValueError(f"mrag_hip.h: cannot read the declaration `{decl}`")
+        for d in parts:
+            t = _ctype(m.group(1), m.group(2), len(d.group(1)), structs, decl)
+            out.append((d.group(2), t * int(d.group(3)) if d.group(3) else t))
+    return out
 
 
-class AttnArgs(Structure):
-    _fields_ = [
-        ("Q", c_void_p), ("K", c_void_p), ("V", c_void_p), ("O", c_void_p), ("resid", c_void_p), ("mask", c_void_p),
-        ("q_sb", c_int64), ("q_ss", c_int64), ("q_sh", c_int64),
-        ("k_sb", c_int64), ("k_ss", c_int64), ("k_sh", c_int64),
-        ("v_sb", c_int64), ("v_ss", c_int64), ("v_sh", c_int64),
-        ("o_sb", c_int64), ("o_ss", c_int64),
-        ("B", c_int32), ("H", c_int32), ("Sq", c_int32), ("Skv", c_int32), ("kv_batch_div", c_int32),
-        ("scale", c_float), ("out_scale", c_float), ("q_prescaled", c_int32),
-        ("workspace", c_void_p), ("workspace_bytes", c_int64), ("tuning", c_int32),
-        ("bias", c_void_p), ("bias_sh", c_int64),
-    ]
+def _value(expr, decl):
+    """an integer literal, a parenthesised negative one, or `a << b`; no eval"""
+    m = re.fullmatch(r"(\d+)|\(\s*(-\d+)\s*\)|(\d+)\s*<<\s*(\d+)", expr.strip())
+    if not m:
+        raise ValueError(f"mrag_hip.h: cannot read the value of `{decl}`")
+    return int(m.group(3)) << int(m.group(4)) if m.group(3) else int(m.group(1) or m.group(2))
 
 
-class AttnVarlenArgs(Structure):
-    _fields_ = [
-        ("Q", c_void_p), ("K", c_void_p), ("V", c_void_p), ("O", c_void_p), ("cu_seqlens", c_void_p),
-        ("q_ss", c_int64), ("q_sh", c_int64), ("k_ss", c_int64), ("k_sh", c_int64), ("v_ss", c_int64), ("v_sh", c_int64), ("o_ss", c_int64),
-        ("B", c_int32), ("H", c_int32), ("total_rows", c_int32), ("max_seqlen", c_int32), ("scale", c_float),
-    ]
+def parse_header(text: str):
+    """The ABI a header's TEXT declares, as three tables in header order:
+         structs    {C name: ctypes.Structure subclass}  from every `typedef struct NAME { ... } NAME;` (a later struct may point at an earlier one)
+         prototypes {name: (restype, [argtypes])}        from every `RET mrag_name(args);`
+         constants  {name: int}                          from every `#define MRAG_X <int>` and every enumerator
+       A type, a value expression or a `mrag_*(` declaration it cannot read raises ValueError: a guessed width would shift a kernel's argument block."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    structs, prototypes, constants = {}, {}, {}
+    for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", text, re.S):
+        structs[m.group(3)] = type(m.group(3), (Structure,), {"_fields_": _fields(m.group(2), structs)})
+    for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(MRAG_\w+)[ \t]+(\S.*)$", text, re.M):
+        constants[m.group(1)] = _value(m.group(2), m.group(0).strip())
+    for m in re.finditer(r"\benum\b\s*\w*\s*\{(.*?)\}", text, re.S):
+        nxt = 0
+        for item in filter(None, (i.strip() for i in m.group(1).split(","))):
+            name, _, expr = (p.strip() for p in item.partition("="))
+            if not re.fullmatch(r"\w+", name):
+                raise ValueError(f"mrag_hip.h: cannot read the enumerator `{item}`")
+            constants[name] = nxt = _value(expr, item) if expr else nxt
+            nxt += 1
+    for m in re.finditer(r"(?<![\w*])(const\s+)?(\w+)\s*(\**)\s*\b(mrag_\w+)\s*\(([^()]*)\)\s*;", text):
+        decl = " ".join(m.group(0).split())
+        args = []
+        for part in (p.strip() for p in m.group(5).split(",")):
+            a = re.fullmatch(r"(const\s+)?(\w+)\b\s*(\**)\s*\b(\w+)", part)
+            if a:
+                args.append(_ctype(a.group(1), a.group(2), len(a.group(3)), structs, decl))
+            elif part != "void" or args:
+                raise ValueError(f"mrag_hip.h: cannot read the parameter `{part}` of `{decl}`")
+        prototypes[m.group(4)] = (_ctype(m.group(1), m.group(2), len(m.group(3)), structs, decl), args)
+    for name in re.findall(r"\b(mrag_\w+)\s*\(", text):
+        if name not in prototypes:
+            raise ValueError(f"mrag_hip.h: `{name}(` is declared in a form the binding cannot read")
+    return structs, prototypes, constants
 
 
-class LnArgs(Structure):
-    _fields_ = [
-        ("x", c_void_p), ("y", c_void_p), ("gamma", c_void_p), ("beta", c_void_p),
-        ("shift0", c_void_p), ("scale0", c_void_p), ("shift1", c_void_p), ("scale1", c_void_p),
-        ("rows", c_int64), ("D", c_int64), ("ldx", c_int64), ("ldy", c_int64),
-        ("rows_per_batch", c_int64), ("split", c_int64), ("mod_stride", c_int64),
-        ("y_rows_per_batch", c_int64), ("y_batch_stride", c_int64),
-        ("eps", c_float), ("rms", c_int32),
-    ]
+with open(os.path.join(_HERE, "..", "include", "mrag_hip.h")) as _fh:          # read once, at import (source_hash() needs it at load anyway)
+    STRUCTS, PROTOTYPES, CONSTANTS = parse_header(_fh.read())
+SYMBOLS = list(PROTOTYPES)            # every entry point the header declares (tests check the .so exports exactly these)
+MRAG_OK, MRAG_EINVAL, MRAG_ENOTSUP = (CONSTANTS[n] for n in ("MRAG_OK", "MRAG_EINVAL", "MRAG_ENOTSUP"))
 
-
-class ResizePatchArgs(Structure):
-    _fields_ = [
-        ("src", c_void_p), ("frame_idx", c_void_p),
-        ("wy", c_void_p), ("y0", c_void_p), ("ny", c_void_p), ("wx", c_void_p), ("x0", c_void_p), ("nx", c_void_p),
-        ("out", c_void_p),
-        ("s_n", c_int64), ("s_t", c_int64), ("s_c", c_int64), ("ldo", c_int64),
-        ("N", c_int32), ("T", c_int32), ("C", c_int32), ("H", c_int32), ("W", c_int32), ("OH", c_int32), ("OW", c_int32),
-        ("taps_y", c_int32), ("taps_x", c_int32), ("pt", c_int32), ("ph", c_int32), ("pw", c_int32), ("src_fp32", c_int32),
-        ("scale", c_float * 4), ("shift", c_float * 4), ("no_tiling", c_int32),
-    ]
-
-
-class ResamplerLayer(Structure):
-    _fields_ = [(n, c_void_p) for n in ("norm1_w", "norm1_b", "norm2_w", "norm2_b", "to_q", "to_kv", "to_out", "ff_ln_w", "ff_ln_b", "ff_w1", "ff_w2")]
-
-
-class ResamplerArgs(Structure):
-    _fields_ = [("x", c_void_p), ("out", c_void_p), ("latents", c_void_p), ("proj_in_w", c_void_p), ("proj_in_b", c_void_p), ("proj_out_w", c_void_p),
-                ("proj_out_b", c_void_p), ("norm_out_w", c_void_p), ("norm_out_b", c_void_p), ("layers", POINTER(ResamplerLayer)),
-                ("workspace", c_void_p), ("workspace_bytes", c_int64)] + [(n, c_int32) for n in ("N", "n1", "nq", "embedding_dim", "dim", "output_dim", "heads",
-                                                                                                    "depth", "ff_dim")] + [("eps", c_float)]
-
-
-class EncoderLayer(Structure):
-    _fields_ = [(n, c_void_p) for n in ("in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "lin1_w", "lin1_b", "lin2_w", "lin2_b", "norm1_w", "norm1_b",
-                                        "norm2_w", "norm2_b")]
-
-
-class CamaEncoderArgs(Structure):
-    _fields_ = [("x", c_void_p), ("out", c_void_p), ("mask", c_void_p), ("layers", POINTER(EncoderLayer)), ("workspace", c_void_p), ("workspace_bytes", c_int64)] + [
-        (n, c_int32) for n in ("B", "L", "d_model", "nhead", "ff_dim", "num_layers")] + [("eps", c_float)]
-
-
-class QkNormRopeArgs(Structure):
-    _fields_ = [
-        ("qkv", c_void_p), ("q_gamma", c_void_p), ("q_beta", c_void_p), ("k_gamma", c_void_p), ("k_beta", c_void_p),
-        ("cos", c_void_p), ("sin", c_void_p),
-        ("B", c_int32), ("S", c_int32), ("H", c_int32), ("text_len", c_int32),
-        ("eps", c_float), ("q_premul", c_float),
-    ]
-
-
-class GroupNormArgs(Structure):
-    _fields_ = [
-        ("x", c_void_p), ("y", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("emb", c_void_p), ("workspace", c_void_p),
-        ("N", c_int64), ("HW", c_int64), ("C", c_int64), ("emb_stride", c_int64),
-        ("G", c_int32), ("chunks", c_int32), ("silu", c_int32), ("eps", c_float),
-        ("mod", c_void_p), ("mod_T", c_int32), ("mod_H", c_int32), ("mod_W", c_int32), ("mod_Tz", c_int32), ("mod_shift", c_int32), ("mod_split", c_int32),
-        ("y_stride_n", c_int64), ("fold", c_int32),
-    ]
-
-
-class ConvArgs(Structure):
-    _fields_ = [
-        ("x", c_void_p), ("W", c_void_p), ("bias", c_void_p), ("y", c_void_p), ("resid", c_void_p),
-        ("N", c_int32), ("H", c_int32), ("Wd", c_int32), ("Cin", c_int32), ("Cout", c_int32),
-        ("stride", c_int32), ("upsample", c_int32), ("mode", c_int32), ("epilogue", c_int32), ("asym_pad", c_int32),
-        ("t_taps", c_int32), ("t_frames", c_int32), ("acc_scale", c_float),
-    ]
-
-
-class ConvFp8Args(Structure):
-    _fields_ = [
-        ("x8", c_void_p), ("W8", c_void_p), ("x_exp", c_void_p), ("w_exp", c_void_p), ("bias", c_void_p), ("y", c_void_p), ("resid", c_void_p),
-        ("N", c_int32), ("H", c_int32), ("Wd", c_int32), ("Cin", c_int32), ("Cout", c_int32),
-        ("stride", c_int32), ("upsample", c_int32), ("asym_pad", c_int32), ("t_taps", c_int32), ("epilogue", c_int32),
-    ]
-
-
-MRAG_OK, MRAG_EINVAL, MRAG_ENOTSUP = 0, -1, -2
+# the argument blocks under the names the package uses
+GemmArgs, GemmFp8Args, FfFusedArgs = STRUCTS["mrag_gemm_args"], STRUCTS["mrag_gemm_fp8_args"], STRUCTS["mrag_ff_fused_args"]
+AttnArgs, AttnVarlenArgs, LnArgs = STRUCTS["mrag_attn_args"], STRUCTS["mrag_attn_varlen_args"], STRUCTS["mrag_ln_args"]
+QkNormRopeArgs, GroupNormArgs = STRUCTS["mrag_qknorm_rope_args"], STRUCTS["mrag_groupnorm_args"]
+ConvArgs, ConvFp8Args, ResizePatchArgs = STRUCTS["mrag_conv_args"], STRUCTS["mrag_conv_fp8_args"], STRUCTS["mrag_resize_patch_args"]
+ResamplerLayer, ResamplerArgs = STRUCTS["mrag_resampler_layer"], STRUCTS["mrag_resampler_args"]
+EncoderLayer, CamaEncoderArgs = STRUCTS["mrag_encoder_layer"], STRUCTS["mrag_cama_encoder_args"]
 
 _lib = None
 
@@ -302,101 +236,9 @@ def lib() -> ctypes.CDLL:
     if have != want:
         raise HipLibraryMissing(f"{LIB_PATH} was built from other sources (stamp {have}, sources beside it {want}): rebuild with "
                                 "`python -m motionrag_amd._lib` -- a stale or variant binary is never loaded silently")
-    L.mrag_dispatch_name.restype = c_char_p
-    L.mrag_dispatch_name.argtypes = [c_int32]
-    L.mrag_dispatch_counts.argtypes = [c_void_p, c_int32]
-    L.mrag_probe_mfma_flops.argtypes = [c_int32]
-    L.mrag_probe_mfma_flops.restype = c_int64
-    L.mrag_probe_mfma_bf16.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int32]
-    L.mrag_probe_mfma_f32_flops.argtypes = [c_int32]
-    L.mrag_probe_mfma_f32_flops.restype = c_int64
-    L.mrag_probe_mfma_f32.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int32]
-    L.mrag_probe_stream_copy.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int32]
-    L.mrag_gemm_bf16.argtypes = [c_void_p, POINTER(GemmArgs)]
-    L.mrag_attn_fwd_bf16.argtypes = [c_void_p, POINTER(AttnArgs)]
-    L.mrag_quant_rows_e4m3.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64]
-    L.mrag_gemm_fp8.argtypes = [c_void_p, POINTER(GemmFp8Args)]
-    L.mrag_fp8_launch_counts.argtypes = [c_void_p, c_int32]
-    L.mrag_layernorm_e4m3.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64]
-    L.mrag_gemm_fp8_k64.argtypes = [c_void_p, POINTER(GemmFp8Args)]
-    L.mrag_gemm_fp8_k64_launch_counts.argtypes = [c_void_p, c_int32]
-    L.mrag_ff_fused_bf16.argtypes = [c_void_p, POINTER(FfFusedArgs)]
-    L.mrag_ff_fused_supported.argtypes = [c_int64, c_int64]
-    L.mrag_ff_fused_launch_counts.argtypes = [c_void_p, c_int32]
-    L.mrag_gemm_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
-    L.mrag_gemm_workspace_bytes.restype = c_int64
-    L.mrag_attn_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
-    L.mrag_attn_workspace_bytes.restype = c_int64
-    L.mrag_attn_fp8_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
-    L.mrag_attn_fp8_workspace_bytes.restype = c_int64
-    L.mrag_attn_fwd_fp8.argtypes = [c_void_p, POINTER(AttnArgs)]
-    L.mrag_attn_joint_fp8_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
-    L.mrag_attn_joint_fp8_workspace_bytes.restype = c_int64
-    L.mrag_attn_joint_fwd_fp8.argtypes = [c_void_p, POINTER(AttnArgs)]
-    L.mrag_attn_small_bf16.argtypes = [c_void_p, POINTER(AttnArgs), c_int32]
-    L.mrag_attn_varlen_fwd_bf16.argtypes = [c_void_p, POINTER(AttnVarlenArgs)]
-    L.mrag_attn_varlen_launch_counts.argtypes = [c_void_p, c_int32]
-    L.mrag_comm_unique_id.argtypes = [c_void_p]
-    L.mrag_comm_init.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]
-    L.mrag_comm_destroy.argtypes = [c_void_p]
-    L.mrag_allgather.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]
-    L.mrag_layernorm_bf16.argtypes = [c_void_p, POINTER(LnArgs)]
-    L.mrag_qknorm_rope_bf16.argtypes = [c_void_p, POINTER(QkNormRopeArgs)]
-    L.mrag_timestep_embedding_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32]
-    L.mrag_silu_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_int64]
-    L.mrag_add_rows_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64]
-    L.mrag_add_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]
-    L.mrag_conv_bf16.argtypes = [c_void_p, POINTER(ConvArgs)]
-    L.mrag_conv_fp8.argtypes = [c_void_p, POINTER(ConvFp8Args)]
-    L.mrag_conv_fp8_launch_counts.argtypes = [c_void_p, c_int32]
-    L.mrag_ip_attn_folded_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64,
-                                           c_int64, c_float, c_float, c_int32]
-    L.mrag_add_bcast_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64]
-    L.mrag_axpby_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float]
-    L.mrag_cfg_euler_step_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int64, c_float, c_float]
-    L.mrag_patchify_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int32] * 7
-    L.mrag_unpatchify_bf16.argtypes = [c_void_p, c_void_p, c_void_p] + [c_int32] * 5
-    L.mrag_cfg_ddim_step_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_int64] + [c_float] * 5
-    L.mrag_topk_workspace_bytes.argtypes = [c_int64, c_int32]
-    L.mrag_topk_workspace_bytes.restype = c_int64
-    L.mrag_topk_workspace_bytes_k.argtypes = [c_int64, c_int32, c_int32]
-    L.mrag_topk_workspace_bytes_k.restype = c_int64
-    L.mrag_topk_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_int32,
-                                c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32]
-    L.mrag_topk_rerank_f32.argtypes = [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32,
-                                       c_void_p, c_void_p, c_void_p]
-    L.mrag_groupnorm_workspace_bytes.argtypes = [c_int64, c_int64, c_int32]
-    L.mrag_groupnorm_workspace_bytes.restype = c_int64
-    L.mrag_groupnorm_bf16.argtypes = [c_void_p, POINTER(GroupNormArgs)]
-    L.mrag_groupnorm_split_workspace_bytes.argtypes = [c_int64, c_int64, c_int32]
-    L.mrag_groupnorm_split_workspace_bytes.restype = c_int64
-    L.mrag_groupnorm_partial_bf16.argtypes = [c_void_p, POINTER(GroupNormArgs), c_void_p]
-    L.mrag_groupnorm_apply_stats_bf16.argtypes = [c_void_p, POINTER(GroupNormArgs), c_void_p, c_int32, c_int64]
-    L.mrag_swap_outer_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64]
-    L.mrag_im2col3x3_bf16.argtypes = [c_void_p, c_void_p, c_void_p] + [c_int32] * 7
-    L.mrag_unfold_t3_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32]
-    L.mrag_geglu_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64]
-    L.mrag_weighted_sum_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_float]
-    L.mrag_ddim_v_step_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + [c_float] * 7
-    L.mrag_ddim_v_rescale_workspace_bytes.argtypes = [c_int64, c_int64]
-    L.mrag_ddim_v_rescale_workspace_bytes.restype = c_int64
-    L.mrag_ddim_v_step_rescaled_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64] + [c_float] * 8 + [c_void_p, c_int64]
-    L.mrag_resize_patchify_bf16.argtypes = [c_void_p, POINTER(ResizePatchArgs)]
-    L.mrag_resampler_workspace_bytes.argtypes = [c_int32] * 7
-    L.mrag_resampler_workspace_bytes.restype = c_int64
-    L.mrag_resampler_fwd.argtypes = [c_void_p, POINTER(ResamplerArgs)]
-    L.mrag_cama_encoder_workspace_bytes.argtypes = [c_int32] * 4
-    L.mrag_cama_encoder_workspace_bytes.restype = c_int64
-    L.mrag_cama_encoder_fwd.argtypes = [c_void_p, POINTER(CamaEncoderArgs)]
-    L.mrag_denormalize_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int32]
-    L.mrag_cfg_dpm_step_bf16.argtypes = [c_void_p] * 5 + [c_int64] + [c_float] * 8 + [c_int32]
-    L.mrag_blend_tile_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int32] * 8
-    L.mrag_softmax_rows_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_float]
-    L.mrag_assemble_tokens_bf16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32]
-    for name in SYMBOLS:          # everything that did not declare a 64-bit / pointer result above returns an int status
+    for name, (restype, argtypes) in PROTOTYPES.items():
         fn = getattr(L, name)
-        if name not in _NON_INT_RESULT:
-            fn.restype = c_int32
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -407,7 +249,7 @@ class HipError(RuntimeError):
 
 def check(rc: int, what: str) -> None:
     if rc != 0:
-        kind = {-1: "MRAG_EINVAL", -2: "MRAG_ENOTSUP"}.get(rc, f"hipError {rc}")
+        kind = {MRAG_EINVAL: "MRAG_EINVAL", MRAG_ENOTSUP: "MRAG_ENOTSUP"}.get(rc, f"hipError {rc}")
         raise HipError(f"{what} failed: {kind}")
 
 

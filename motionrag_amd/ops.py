@@ -12,22 +12,37 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import AttnArgs, AttnVarlenArgs, FfFusedArgs, GemmArgs, GemmFp8Args, LnArgs, QkNormRopeArgs, check
+from ._lib import AttnArgs, AttnVarlenArgs, ConvArgs, ConvFp8Args, FfFusedArgs, GemmArgs, GemmFp8Args, GroupNormArgs, LnArgs, QkNormRopeArgs, check
 
-EPI_NONE, EPI_GELU_TANH, EPI_GELU_ERF, EPI_RESID, EPI_GATE_RESID, EPI_SILU, EPI_GEGLU, EPI_QKNORM_ROPE = range(8)
+
+def _header(prefix: str, *names: str):
+    """the values include/mrag_hip.h gives MRAG_<prefix><name>, which documents each of them; a name it lacks is a KeyError at import"""
+    return (_lib.CONSTANTS["MRAG_" + prefix + n] for n in names)
+
+
+EPI_NONE, EPI_GELU_TANH, EPI_GELU_ERF, EPI_RESID, EPI_GATE_RESID, EPI_SILU, EPI_GEGLU, EPI_QKNORM_ROPE = _header(
+    "EPI_", "NONE", "GELU_TANH", "GELU_ERF", "RESID", "GATE_RESID", "SILU", "GEGLU", "QKNORM_ROPE")
+GEMM_TUNE_NO_WIDE, GEMM_TUNE_NO_STAGED, GEMM_TUNE_GEGLU_NO_STAGED, GEMM_TUNE_STREAMK, GEMM_TUNE_NO_W4, GEMM_TUNE_NO_SKINNY, GEMM_TUNE_TAIL_RECT = _header(
+    "GEMM_TUNE_", "NO_WIDE", "NO_STAGED", "GEGLU_NO_STAGED", "STREAMK", "NO_W4", "NO_SKINNY", "TAIL_RECT")
+ATTN_TUNE_NO_TINY, ATTN_TUNE_LEGACY, ATTN_TUNE_FP8_QUANT_ONLY = _header("ATTN_TUNE_", "NO_TINY", "LEGACY", "FP8_QUANT_ONLY")
+CONV_3X3, CONV_T3 = _header("CONV_", "3X3", "T3")
+FF_FUSED_ROWS = _lib.CONSTANTS["MRAG_FF_FUSED_ROWS"]   # rows per workgroup of mrag_ff_fused_bf16; its grid is ceil(rows / FF_FUSED_ROWS), neither persistent nor capped
 LOG2E = 1.4426950408889634
 
-
-# Developer tuning knobs (tools/microbench.py, A/B tests): explicit `tuning` fields of the C-ABI argument structs, 0 = the shipped behaviour.
-# Nothing on the launch path reads the environment.
+# Developer tuning knobs (tools/microbench.py, A/B tests): explicit `tuning` fields of the C-ABI argument structs (the *_TUNE_* bits above), 0 = the
+# shipped behaviour.  Nothing on the launch path reads the environment.
 TUNING = {"gemm": 0, "attn": 0, "attn_no_split": False, "no_qkv_fuse": False, "no_batched_w": False, "gn_fold": False}
-GEMM_TUNE_NO_WIDE, GEMM_TUNE_NO_STAGED, GEMM_TUNE_GEGLU_NO_STAGED = 1, 2, 4
-ATTN_TUNE_NO_TINY, ATTN_TUNE_LEGACY = 1, 8
-ATTN_TUNE_FP8_QUANT_ONLY = 16   # mrag_attn_joint_fwd_fp8 stops after amax + quantise (tools/attn_fp8_joint_measure.py)
 
 
 class HipOnly(RuntimeError):
     """Raised when an op is handed a tensor that is not on the GPU (no CPU fallback exists)."""
+
+
+def _launch_counts(entry: str, n: int) -> list:
+    """the `n` host-side launch counters behind one of the mrag_*_launch_counts entry points"""
+    buf = (ctypes.c_uint64 * n)()
+    getattr(_lib.lib(), entry)(buf, n)
+    return [int(v) for v in buf]
 
 
 def dispatch_counts() -> dict:
@@ -158,10 +173,6 @@ def _gemm_workspace(a: "GemmArgs", device: torch.device) -> None:
 
 
 M_SK_MIN_ROWS = 4096          # below this no 256x256 grid reaches a second round: skip the query
-GEMM_TUNE_STREAMK = 8
-GEMM_TUNE_NO_W4 = 1 << 16      # keep long-K linears on the 8-wave 256x256 tile (A/B knob; default: the persistent four-wave kernel where it applies)
-GEMM_TUNE_NO_SKINNY = 1 << 17  # keep few-row problems (M <= 256) on the tiled kernels (tests pin one kernel family with it)
-GEMM_TUNE_TAIL_RECT = 1 << 19  # opt-in: a small partial last round of the persistent GEMM as its own launch of 128x128 tiles (measured equal: DESIGN 3.7d)
 
 
 def ip_attn_folded_(scores: torch.Tensor, v: torch.Tensor, hidden: torch.Tensor, H: int, keys: int, kv_batch_div: int = 1, scale: float = 0.125,
@@ -346,9 +357,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, out: Optiona
 
 def attn_varlen_launch_counts() -> int:
     """launches of mrag_attn_varlen_fwd_bf16 so far (mrag_attn_varlen_launch_counts; refused calls do not count)"""
-    buf = (ctypes.c_uint64 * 1)()
-    _lib.lib().mrag_attn_varlen_launch_counts(buf, 1)
-    return int(buf[0])
+    return _launch_counts("mrag_attn_varlen_launch_counts", 1)[0]
 
 
 def attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: int, *, out: Optional[torch.Tensor] = None,
@@ -512,9 +521,7 @@ def qkv_linear_qknorm_rope(x: torch.Tensor, weight: torch.Tensor, bias: Optional
 
 def fp8_launch_counts() -> dict:
     """launches of the fp8 linear path's two entry points so far (host-side counters beside the dispatch table): {"gemm": n, "quant": n}"""
-    buf = (ctypes.c_uint64 * 2)()
-    _lib.lib().mrag_fp8_launch_counts(buf, 2)
-    return {"gemm": int(buf[0]), "quant": int(buf[1])}
+    return dict(zip(("gemm", "quant"), _launch_counts("mrag_fp8_launch_counts", 2)))
 
 
 def fp8_linear_supported(N: int, K: int) -> bool:
@@ -599,9 +606,7 @@ def linear_fp8(x: torch.Tensor, w8: torch.Tensor, w_exp: torch.Tensor, bias: Opt
 
 def fp8_k64_launch_counts() -> dict:
     """launches of the feed-forward fp8 path's two entry points so far (mrag_gemm_fp8_k64_launch_counts): {"gemm": n, "ln": n}"""
-    buf = (ctypes.c_uint64 * 2)()
-    _lib.lib().mrag_gemm_fp8_k64_launch_counts(buf, 2)
-    return {"gemm": int(buf[0]), "ln": int(buf[1])}
+    return dict(zip(("gemm", "ln"), _launch_counts("mrag_gemm_fp8_k64_launch_counts", 2)))
 
 
 def fp8_linear_k64_supported(N: int, K: int, epilogue: int = EPI_NONE) -> bool:
@@ -670,7 +675,6 @@ def linear_fp8_k64(x, w8: torch.Tensor, w_exp: torch.Tensor, bias: Optional[torc
     return out
 
 
-FF_FUSED_ROWS = 128          # rows per workgroup of mrag_ff_fused_bf16 (MRAG_FF_FUSED_ROWS); its grid is ceil(rows / FF_FUSED_ROWS), neither persistent nor capped
 FF_FUSED_MAX_INNER = 1 << 20
 
 
@@ -681,9 +685,7 @@ def ff_fused_supported(C: int, inner: int) -> bool:
 
 def ff_fused_launches() -> int:
     """launches of mrag_ff_fused_bf16 so far (mrag_ff_fused_launch_counts; refused calls do not count)"""
-    buf = (ctypes.c_uint64 * 1)()
-    _lib.lib().mrag_ff_fused_launch_counts(buf, 1)
-    return int(buf[0])
+    return _launch_counts("mrag_ff_fused_launch_counts", 1)[0]
 
 
 def ff_fused(x: torch.Tensor, ln_weight: Optional[torch.Tensor], ln_bias: Optional[torch.Tensor], eps: float, w1_interleaved: torch.Tensor,
@@ -1047,7 +1049,6 @@ def groupnorm(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[tor
     `mod` [N, Tz, hz, wz, 2C] + `mod_geom` = (T, H, W, shift, split): the spatially conditioned form gn(x) * mod[.., :C] + mod[.., C:] with the
     latent-resolution maps read through the nearest-neighbour frame / pixel map (mrag_hip.h); `out` may then be a [N, HW, C] view whose
     sample stride is larger than HW * C (the frames behind a causal convolution's context frames)."""
-    from ._lib import GroupNormArgs
     _dev(x, name="x")
     if x.dim() != 3 or not x.is_contiguous():
         raise ValueError("groupnorm: contiguous [N, HW, C] required")
@@ -1079,10 +1080,7 @@ def groupnorm(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[tor
     return out
 
 
-
-
 def _gn_split_args(x: torch.Tensor, groups: int):
-    from ._lib import GroupNormArgs
     _dev(x, name="x")
     if x.dim() != 3 or not x.is_contiguous():
         raise ValueError("groupnorm: contiguous [N, HW, C] required")
@@ -1139,9 +1137,6 @@ def swap_outer(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Ten
     return out
 
 
-CONV_3X3, CONV_T3 = 1, 2
-
-
 def conv_implicit(x: torch.Tensor, wk: torch.Tensor, bias: Optional[torch.Tensor], mode: int, *, stride: int = 1, upsample: bool = False,
                   frames: int = 0, resid: Optional[torch.Tensor] = None, asym_pad: bool = False, t_frames: int = 0, acc_scale: float = 1.0) -> torch.Tensor:
     """implicit-GEMM convolution (no materialised im2col), Cin % 64 == 0.
@@ -1149,7 +1144,6 @@ def conv_implicit(x: torch.Tensor, wk: torch.Tensor, bias: Optional[torch.Tensor
               t_frames = T > 0: causal 3x3x3 -- x [S (T + 2), H, W, Cin] (two context frames in front of each sample's T frames) -> [S T, H, W, Cout],
               wk [Cout, 27 Cin] in (kt, ky, kx, cin) order.
     CONV_T3:  x [(b t), HW, Cin] with `frames` = t -> same rows x Cout, wk [Cout, 3 Cin] in (kt, cin) order."""
-    from ._lib import ConvArgs
     _dev(x, name="x"); _dev(wk, name="weight")
     if not x.is_contiguous() or not wk.is_contiguous():
         raise ValueError("conv_implicit: contiguous activation and weight required")
@@ -1194,9 +1188,7 @@ def conv_implicit(x: torch.Tensor, wk: torch.Tensor, bias: Optional[torch.Tensor
 
 def conv_fp8_launch_counts() -> dict:
     """launches of the fp8 convolution so far (host-side counter, mrag_conv_fp8_launch_counts): {"conv": n}"""
-    buf = (ctypes.c_uint64 * 1)()
-    _lib.lib().mrag_conv_fp8_launch_counts(buf, 1)
-    return {"conv": int(buf[0])}
+    return {"conv": _launch_counts("mrag_conv_fp8_launch_counts", 1)[0]}
 
 
 def conv_fp8_supported(N: int, H: int, W: int, Cin: int, Cout: int, stride: int = 1, upsample: bool = False) -> bool:
@@ -1218,7 +1210,6 @@ def conv_implicit_fp8(x: torch.Tensor, w8: torch.Tensor, w_exp: torch.Tensor, bi
     grow-only workspace of the (device, stream); (w8, w_exp) = quant_rows_e4m3 of the [Cout, 9 Cin] tap-major weight, once per output channel.
     `resid` (the output's shape) rides in the epilogue; `out` may be `resid`.  Two launches, nothing read back: capturable into a HIP graph.  Raises on shapes the kernel does
     not take (`conv_fp8_supported`)."""
-    from ._lib import ConvFp8Args
     _dev(x, name="x"); _dev(w8, torch.uint8, "w8"); _dev(w_exp, torch.int32, "w_exp")
     if bias is not None:
         _dev(bias, name="bias")

@@ -2,8 +2,11 @@
 host-side logic (scheduler tables, RoPE tables, masks, retrieval table I/O), and the product path's refusal to run
 without the GPU."""
 import ctypes
+import functools
 import os
 import re
+import subprocess
+import tempfile
 
 import numpy as np
 import pytest
@@ -12,15 +15,74 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+# the package's name for every argument struct the header declares
+STRUCT_ALIASES = {
+    "GemmArgs": "mrag_gemm_args", "GemmFp8Args": "mrag_gemm_fp8_args", "FfFusedArgs": "mrag_ff_fused_args", "AttnArgs": "mrag_attn_args",
+    "AttnVarlenArgs": "mrag_attn_varlen_args", "LnArgs": "mrag_ln_args", "ResizePatchArgs": "mrag_resize_patch_args",
+    "ResamplerLayer": "mrag_resampler_layer", "ResamplerArgs": "mrag_resampler_args", "EncoderLayer": "mrag_encoder_layer",
+    "CamaEncoderArgs": "mrag_cama_encoder_args", "QkNormRopeArgs": "mrag_qknorm_rope_args", "GroupNormArgs": "mrag_groupnorm_args",
+    "ConvArgs": "mrag_conv_args", "ConvFp8Args": "mrag_conv_fp8_args"}
+# every header constant ops.py takes from the table, under its Python name
+OPS_CONSTANTS = ("EPI_NONE", "EPI_GELU_TANH", "EPI_GELU_ERF", "EPI_RESID", "EPI_GATE_RESID", "EPI_SILU", "EPI_GEGLU", "EPI_QKNORM_ROPE",
+                 "GEMM_TUNE_NO_WIDE", "GEMM_TUNE_NO_STAGED", "GEMM_TUNE_GEGLU_NO_STAGED", "GEMM_TUNE_STREAMK", "GEMM_TUNE_NO_W4", "GEMM_TUNE_NO_SKINNY",
+                 "GEMM_TUNE_TAIL_RECT", "ATTN_TUNE_NO_TINY", "ATTN_TUNE_LEGACY", "ATTN_TUNE_FP8_QUANT_ONLY", "CONV_3X3", "CONV_T3", "FF_FUSED_ROWS")
+
+
+def _header_text():
+    with open(os.path.join(ROOT, "include", "mrag_hip.h")) as fh:
+        return fh.read()
+
+
+@functools.lru_cache(maxsize=None)
+def _compiler_view():
+    """what the C compiler makes of include/mrag_hip.h: ({struct: sizeof}, {(struct, field): (offsetof, sizeof)}, {constant: value}), from a generated C11
+    host program that names every struct, field and constant the binding derived (a name the header lacks does not compile)"""
+    from motionrag_amd import _lib
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "mrag_hip.h"', "int main(void) {"]
+    for cname, st in _lib.STRUCTS.items():
+        lines.append(f'  printf("S {cname} - %zu 0\\n", sizeof({cname}));')
+        for field, _ in st._fields_:
+            lines.append(f'  printf("F {cname} {field} %zu %zu\\n", offsetof({cname}, {field}), sizeof((({cname}*)0)->{field}));')
+    for name in _lib.CONSTANTS:
+        lines.append(f'  printf("C {name} - %lld 0\\n", (long long){name});')
+    lines += ["  return 0;", "}"]
+    with tempfile.TemporaryDirectory() as tmp:
+        src, exe = os.path.join(tmp, "abi_probe.c"), os.path.join(tmp, "abi_probe")
+        with open(src, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+        subprocess.run(["/opt/rocm/llvm/bin/clang", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe],
+                       check=True, capture_output=True, text=True, timeout=120)
+        out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=60).stdout
+    sizes, fields, consts = {}, {}, {}
+    for kind, owner, field, a, b in (ln.split() for ln in out.splitlines()):
+        if kind == "S":
+            sizes[owner] = int(a)
+        elif kind == "F":
+            fields[owner, field] = (int(a), int(b))
+        else:
+            consts[owner] = int(a)
+    return sizes, fields, consts
+
+
 def test_library_exports_every_declared_symbol():
     from motionrag_amd import _lib
     _lib.build()
-    hdr = open(os.path.join(ROOT, "include", "mrag_hip.h")).read()
+    hdr = _header_text()
     declared = sorted(set(re.findall(r"\b(mrag_[a-z0-9_]+)\s*\(", hdr)))
-    assert declared == sorted(_lib.SYMBOLS), (declared, sorted(_lib.SYMBOLS))
+    assert declared == sorted(_lib.SYMBOLS), (declared, sorted(_lib.SYMBOLS))       # the binding's reader against an independent scan of the header
     L = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(L, name), name
+    # and the reverse: the library defines no mrag_* function the header does not declare.  Its one exported mrag_* DATA object is the launch-counter
+    # table the translation units share (csrc/common.h), which nothing binds.
+    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True, timeout=60).stdout
+    exported = {}
+    for line in nm.splitlines():
+        parts = line.split()
+        if parts[-1].startswith("mrag_"):
+            exported.setdefault(parts[-2], set()).add(parts[-1])
+    assert sorted(exported.pop("T")) == declared
+    assert exported == {"B": {"mrag_dispatch_table"}}, exported
     lib = _lib.lib()
     assert lib.mrag_abi_version() == _lib.ABI_VERSION and lib.mrag_target_arch() == b"gfx950"
     assert lib.mrag_topk_workspace_bytes(10000, 256) > 0
@@ -31,34 +93,105 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_struct_layouts_match_the_header():
-    """field order / count of the ctypes structs follows the header's typedefs"""
+    """every ctypes struct has the layout the C compiler gives the header's typedef: size of the struct, offset and size of every field"""
     from motionrag_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "mrag_hip.h")).read()
-    for cname, st in (("mrag_gemm_args", _lib.GemmArgs), ("mrag_attn_args", _lib.AttnArgs), ("mrag_ln_args", _lib.LnArgs),
-                      ("mrag_qknorm_rope_args", _lib.QkNormRopeArgs), ("mrag_groupnorm_args", _lib.GroupNormArgs), ("mrag_conv_args", _lib.ConvArgs)):
+    hdr = re.sub(r"/\*.*?\*/", "", _header_text(), flags=re.S)
+    declared = re.findall(r"\btypedef\s+struct\s+(\w+)", hdr)
+    assert declared == list(_lib.STRUCTS) and len(declared) == 15
+    assert sorted(STRUCT_ALIASES.values()) == sorted(declared)                      # the header declares no struct without an alias
+    for alias, cname in STRUCT_ALIASES.items():
+        assert getattr(_lib, alias) is _lib.STRUCTS[cname], alias
+    sizes, fields, _ = _compiler_view()
+    n_fields = 0
+    for cname, st in _lib.STRUCTS.items():
+        assert issubclass(st, ctypes.Structure) and ctypes.sizeof(st) == sizes[cname], (cname, ctypes.sizeof(st), sizes[cname])
+        # field order / count follows the typedef: an independent reading of the body's declarator names
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), hdr, re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if not decl:
-                continue
-            for part in decl.split(","):
-                names.append(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part)[-1])
+        names = [re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part.split("[")[0])[-1] for decl in body.split(";") if decl.strip() for part in decl.split(",")]
         assert names == [f[0] for f in st._fields_], (cname, names)
+        for field, _ in st._fields_:
+            d = getattr(st, field)
+            assert (d.offset, d.size) == fields[cname, field], (cname, field, d.offset, d.size, fields[cname, field])
+            n_fields += 1
+    assert n_fields == len(fields) == 297
 
 
 def test_tuning_constants_match_the_header():
-    """the developer knobs ops.py passes in `tuning` are the header's enumerators (one set of meanings on both sides of the C ABI)"""
-    import re
-    from motionrag_amd import ops
-    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mrag_hip.h")).read()
-    vals = {}
-    for name, expr in re.findall(r"(MRAG_(?:GEMM|ATTN)_TUNE_\w+)\s*=\s*([^,}/]+)", hdr):
-        vals[name] = eval(expr.strip(), {}, {})          # "8", "1 << 16"
-    for py in ("GEMM_TUNE_NO_WIDE", "GEMM_TUNE_NO_STAGED", "GEMM_TUNE_GEGLU_NO_STAGED", "GEMM_TUNE_STREAMK", "GEMM_TUNE_NO_W4", "GEMM_TUNE_NO_SKINNY", "GEMM_TUNE_TAIL_RECT",
-               "ATTN_TUNE_NO_TINY", "ATTN_TUNE_LEGACY"):
-        assert vals["MRAG_" + py] == getattr(ops, py), py
+    """every constant ops.py takes from the header (epilogue ids, `tuning` bits, convolution modes, the fused feed-forward's rows) and every MRAG_* constant
+    the binding derived carry the value the C compiler gives them (one set of meanings on both sides of the C ABI)"""
+    from motionrag_amd import _lib, ops
+    _, _, consts = _compiler_view()
+    assert consts == _lib.CONSTANTS and all(n.startswith("MRAG_") for n in consts)
+    for py in OPS_CONSTANTS:
+        assert consts["MRAG_" + py] == getattr(ops, py), py
+    assert (_lib.MRAG_OK, _lib.MRAG_EINVAL, _lib.MRAG_ENOTSUP) == (consts["MRAG_OK"], consts["MRAG_EINVAL"], consts["MRAG_ENOTSUP"]) == (0, -1, -2)
+    # the implicit-increment enumerators: mrag_kernel_id counts itself, and the library names as many kernels
+    kernel_ids = [n for n in consts if n.startswith("MRAG_K_") and n != "MRAG_K_COUNT"]
+    assert sorted(consts[n] for n in kernel_ids) == list(range(consts["MRAG_K_COUNT"]))
+    hdr = re.sub(r"/\*.*?\*/", "", _header_text(), flags=re.S)
+    assert set(re.findall(r"\bMRAG_[A-Z0-9][A-Za-z0-9_]*\b", hdr)) - {"MRAG_HIP_H"} == set(consts)      # no constant of the header went unread
+
+
+def test_mixed_width_signatures_are_pinned():
+    """entry points that mix 32-bit, 64-bit, float and pointer arguments, written out by hand: the derived binding must come out exactly so"""
+    from ctypes import POINTER, c_char_p, c_float, c_int32, c_int64, c_void_p
+    from motionrag_amd import _lib
+    want = {
+        "mrag_topk_f32": (c_int32, [c_void_p] * 3 + [c_int64, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
+                                    c_int32, c_int32]),
+        "mrag_cfg_dpm_step_bf16": (c_int32, [c_void_p] * 5 + [c_int64] + [c_float] * 8 + [c_int32]),
+        "mrag_layernorm_e4m3": (c_int32, [c_void_p] * 4 + [c_float, c_void_p, c_void_p] + [c_int64] * 4),
+        "mrag_groupnorm_apply_stats_bf16": (c_int32, [c_void_p, POINTER(_lib.GroupNormArgs), c_void_p, c_int32, c_int64]),
+        "mrag_comm_init": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_void_p)]),
+        "mrag_probe_mfma_flops": (c_int64, [c_int32]),
+        "mrag_dispatch_name": (c_char_p, [c_int32]),
+        "mrag_abi_version": (c_int32, []),
+    }
+    _lib.build()
+    L = _lib.lib()
+    for name, (restype, argtypes) in want.items():
+        assert _lib.PROTOTYPES[name] == (restype, argtypes), (name, _lib.PROTOTYPES[name])
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, (name, fn.restype, fn.argtypes)
+    for name in _lib.SYMBOLS:                                                        # lib() bound every prototype, in the derived form
+        fn = getattr(L, name)
+        assert (fn.restype, list(fn.argtypes)) == _lib.PROTOTYPES[name], name
+
+
+def test_header_reader_refuses_what_it_cannot_map():
+    """parse_header on synthetic header text: it never guesses a width, a value or a prototype"""
+    from motionrag_amd._lib import parse_header
+    for field in ("double x", "size_t n"):
+        with pytest.raises(ValueError, match=field):
+            parse_header("typedef struct mrag_t { int32_t a; %s; } mrag_t;" % field)
+    with pytest.raises(ValueError, match="double x"):
+        parse_header("int mrag_f(void* stream, double x);")
+    with pytest.raises(ValueError, match=r"FOO \+ 1"):
+        parse_header("enum { FOO = 1, BAR = FOO + 1 };")
+    with pytest.raises(ValueError, match="MRAG_N"):
+        parse_header("#define MRAG_N sizeof(int)\n")
+    with pytest.raises(ValueError, match="mrag_x"):
+        parse_header("int mrag_x(struct y v);")
+    with pytest.raises(ValueError, match="mrag_cb"):
+        parse_header("int mrag_cb(void (*fn)(int), int32_t n);")                   # a declaration no prototype was parsed for
+    structs, protos, consts = parse_header("""
+        #define MRAG_ROWS 128   /* rows */
+        #define MRAG_EBAD (-3)
+        enum mrag_id { MRAG_A = 2, MRAG_B, MRAG_C /* c */, MRAG_BIT = 1 << 17, MRAG_AFTER };
+        typedef struct mrag_inner { const void *a, *b; float s[4]; int32_t n; } mrag_inner;
+        typedef struct mrag_outer { const mrag_inner* layers; int64_t M, N; const uint8_t* mask; } mrag_outer;
+        int64_t mrag_bytes(int64_t M, /* rows */
+                           int32_t n);
+        const char* mrag_name(void);
+        int mrag_run(void* stream, const mrag_outer* args, void** out, uint64_t seed, const char* tag);
+        """)
+    assert consts == {"MRAG_ROWS": 128, "MRAG_EBAD": -3, "MRAG_A": 2, "MRAG_B": 3, "MRAG_C": 4, "MRAG_BIT": 1 << 17, "MRAG_AFTER": (1 << 17) + 1}
+    inner, outer = structs["mrag_inner"], structs["mrag_outer"]
+    assert list(structs) == ["mrag_inner", "mrag_outer"]
+    assert inner._fields_ == [("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("s", ctypes.c_float * 4), ("n", ctypes.c_int32)]
+    assert outer._fields_ == [("layers", ctypes.POINTER(inner)), ("M", ctypes.c_int64), ("N", ctypes.c_int64), ("mask", ctypes.c_void_p)]
+    assert protos == {"mrag_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32]), "mrag_name": (ctypes.c_char_p, []),
+                      "mrag_run": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(outer), ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint64, ctypes.c_char_p])}
 
 
 def test_ops_refuse_cpu_tensors():

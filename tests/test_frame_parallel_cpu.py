@@ -1,5 +1,6 @@
 """CPU suite of the frame-parallel (tier 2) DynamiCrafter UNet: the C ABI of the split GroupNorm and the swap copy is bound as declared, `FrameParallel`'s
 geometry, and its three exchanges over a four-rank gloo group on CPU tensors."""
+import ctypes
 import os
 import re
 import sys
@@ -26,7 +27,7 @@ def test_new_prototypes_are_bound_with_matching_argument_counts():
         assert name in _lib.SYMBOLS and hasattr(L, name)
         fn = getattr(L, name)
         assert fn.argtypes is not None and len(fn.argtypes) == n_args, (name, n_args, fn.argtypes)
-        assert (name in _lib._NON_INT_RESULT) == (m.group(1) == "int64_t"), name
+        assert fn.restype is (ctypes.c_int64 if m.group(1) == "int64_t" else ctypes.c_int32), name
     # the split form's workspace holds what the unsplit form's does (chunk partials + per-(n, c) scale / shift behind the 16 KiB in front)
     assert L.mrag_groupnorm_split_workspace_bytes(2, 320, 1024) >= 16384 + (2 * 1024 * 320 * 2 + 2 * 320 * 2) * 4
     assert _lib.ABI_VERSION == 11                                             # additive: the ABI number stays
