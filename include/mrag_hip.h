@@ -538,6 +538,18 @@ int mrag_weighted_sum_bf16(void* stream, const void* x, const float* w, void* ou
  * resid / kv_batch_div / q_prescaled: MRAG_ENOTSUP).  First user: the CLIP-ViT-H image encoder of the SVD path (257 tokens, 16 heads of 80; transformers
  * CLIPVisionModelWithProjection behind StableVideoDiffusionPipeline._encode_image, src/projects/svd/pipelines/pipeline.py:113-119) -- once per clip.     */
 int mrag_attn_small_bf16(void* stream, const mrag_attn_args* args, int32_t head_dim);
+/* The same product on the matrix pipe, at the same head dims (32, 80, 96, 128) and ANY Sq, Skv >= 1 (attn_hd.hip): flash style with online softmax, K and V
+ * streamed through LDS in 64-key tiles, one workgroup of two waves per (batch, head, 64 query rows) -- Sq = 257 gives 5 workgroups per head, the ragged
+ * last one among them.  v_mfma_f32_32x32x16_bf16 for both products; 80 runs its second product as a zero-padded 96 whose padding exists in LDS only: no byte
+ * beyond the head_dim columns of a row is read or written in global memory, so views of a fused [B, S, 3, H, D] buffer work.  fp32 scores and statistics,
+ * P rounded to bf16 for the second product, fp32 accumulation, one bf16 rounding of the output.  Argument struct and checks as mrag_attn_small_bf16:
+ * MRAG_EINVAL for a null args / Q / K / V / O or B, H, Sq, Skv <= 0; then MRAG_ENOTSUP for mask, bias, resid, kv_batch_div != 1, q_prescaled, a head_dim
+ * outside the set or more than 2^31 - 1 workgroups; then MRAG_EINVAL for Q / K / V / O not 16-byte aligned or a stride not a multiple of 8 elements.
+ * Every check returns before any launch.  No workspace; graph-capturable.                                                                               */
+int mrag_attn_hd_fwd_bf16(void* stream, const mrag_attn_args* args, int32_t head_dim);
+/* host-side relaxed launch counter in the form of mrag_attn_varlen_launch_counts: ONE slot, the launches of mrag_attn_hd_fwd_bf16 (not its refusals).
+ * Copies min(n, 1) slots into out_host (HOST memory), returns 1; answers without a device.  enum mrag_kernel_id keeps its enumerators.              */
+int mrag_attn_hd_launch_counts(uint64_t* out_host, int32_t n);
 
 /* ------------------------------------------------------------------------ */
 /* CAMA building blocks as native launch sequences (`resampler_fwd`, `cama_encoder_fwd`).  No kernel of their own: they issue the launches

@@ -6,7 +6,8 @@ class's state-dict keys (`vision_model.embeddings.{class_embedding, patch_embedd
 `vision_model.encoder.layers.N.{self_attn.{q,k,v,out}_proj, layer_norm1, mlp.fc1, mlp.fc2, layer_norm2}`, `vision_model.post_layernorm`, `visual_projection.weight`).
 
 Head dim 80 is outside the flash kernels (built for 64): the attention of this once-per-clip encoder runs on `mrag_attn_small_bf16` (K / V of a head resident in LDS,
-fp32 FMAs); a tower with head_dim 64 (CLIP-L) takes the flash kernel.  Everything else is the ViT path of motionrag_amd/encoders.py: pixel rows -> patch GEMM ->
+fp32 FMAs) or, after `set_attention_kernel(module, "mfma")` and for every sequence the former refuses (577 tokens at 336 px), on the MFMA kernel
+`mrag_attn_hd_fwd_bf16`; a tower with head_dim 64 (CLIP-L) takes the flash kernel.  Everything else is the ViT path of motionrag_amd/encoders.py: pixel rows -> patch GEMM ->
 token assembly -> LayerNorm / fused QKV GEMM / attention / output and MLP GEMMs with the residuals in their epilogues."""
 from typing import Optional
 
@@ -16,6 +17,21 @@ from torch import nn
 from . import ops
 from .encoders import assemble_tokens, pixels_to_patch_rows
 from .layers import CACHE, Holder, bf16, prenorm_block
+
+
+ATTENTION_KERNELS = ("fma", "mfma")
+
+
+def set_attention_kernel(module: nn.Module, kernel: str = "fma") -> nn.Module:
+    """'fma' (as without this option: `ops.attention_small` wherever it takes the shape) or 'mfma': the attention of every CLIP vision tower under `module`
+    (CLIPVisionModelWithProjection, OpenCLIPVisual, also inside a FrozenOpenCLIPImageEmbedderV2) at a head dim other than 64 runs on the MFMA kernel
+    (`ops.attention_hd`).  Sequences that `attention_small` refuses take the MFMA kernel either way; head_dim-64 towers stay on the flash kernel.  Returns the module."""
+    if kernel not in ATTENTION_KERNELS:
+        raise ValueError("kernel must be 'fma' or 'mfma'")
+    for m in module.modules():
+        if isinstance(m, (CLIPVisionModelWithProjection, OpenCLIPVisual, FrozenOpenCLIPImageEmbedderV2)):
+            m.attention_kernel = kernel
+    return module
 
 
 class _Layer(nn.Module):
@@ -37,6 +53,7 @@ class CLIPVisionOutput:
 
 class CLIPVisionModelWithProjection(nn.Module):
     """defaults = the CLIP-ViT-H/14 image encoder of stable-video-diffusion-img2vid(-xt)"""
+    attention_kernel = "fma"           # set_attention_kernel
 
     def __init__(self, hidden_size=1280, intermediate_size=5120, num_hidden_layers=32, num_attention_heads=16, image_size=224, patch_size=14, projection_dim=1024,
                  num_channels=3, hidden_act="gelu", layer_norm_eps=1e-5, **_unused):
@@ -65,7 +82,7 @@ class CLIPVisionModelWithProjection(nn.Module):
         vm = self.vision_model
         layers = self._layers()
         x = _tower(pixel_values, vm.embeddings.patch_embedding, vm.embeddings.class_embedding, vm.embeddings.position_embedding.weight, vm.pre_layrnorm, layers,
-                   self.heads, self.head_dim, self.patch_size, self.eps, id(self))
+                   self.heads, self.head_dim, self.patch_size, self.eps, id(self), self.attention_kernel)
         pooled = ops.layernorm(x[:, 0].contiguous(), bf16(vm.post_layernorm.weight), bf16(vm.post_layernorm.bias), self.eps)
         return CLIPVisionOutput(ops.linear(pooled, bf16(self.visual_projection.weight)), x)
 
@@ -96,12 +113,12 @@ class CLIPVisionModelWithProjection(nn.Module):
         rows = pixels_to_patch_rows(image_pm1[:, None].contiguous(), resize=size, crop=size, mode="kornia-bicubic", patch=(1, self.patch_size, self.patch_size),
                                     mean=self.MEAN, std=self.STD)
         x = _tower_from_rows(rows, B, size // self.patch_size, vm.embeddings.patch_embedding, vm.embeddings.class_embedding, vm.embeddings.position_embedding.weight,
-                             vm.pre_layrnorm, self._layers(), self.heads, self.head_dim, self.eps, id(self))
+                             vm.pre_layrnorm, self._layers(), self.heads, self.head_dim, self.eps, id(self), self.attention_kernel)
         pooled = ops.layernorm(x[:, 0].contiguous(), bf16(vm.post_layernorm.weight), bf16(vm.post_layernorm.bias), self.eps)
         return CLIPVisionOutput(ops.linear(pooled, bf16(self.visual_projection.weight)), x)
 
 
-def _tower(pixel_values, conv, class_embedding, positional, ln_pre, layers, heads, head_dim, ps, eps, owner_id) -> torch.Tensor:
+def _tower(pixel_values, conv, class_embedding, positional, ln_pre, layers, heads, head_dim, ps, eps, owner_id, attn_kernel="fma") -> torch.Tensor:
     """patch embedding -> [cls] + positions -> ln_pre -> pre-LN residual attention blocks; returns every token BEFORE the post LayerNorm (transformers'
     `last_hidden_state`, open_clip's `visual.transformer` output).  `layers`: (ln_1, fused qkv weight, fused qkv bias, out_proj, ln_2, fc1, fc2) per block."""
     if not pixel_values.is_cuda:
@@ -111,10 +128,10 @@ def _tower(pixel_values, conv, class_embedding, positional, ln_pre, layers, head
     if H != W or H % ps:
         raise ValueError("square inputs with a whole number of patches expected")
     rows = pixels_to_patch_rows(pixel_values[:, None], resize=H, crop=H, mode="bilinear", patch=(1, ps, ps), mean=(0.5,) * C, std=(0.5,) * C)   # identity geometry
-    return _tower_from_rows(rows, B, H // ps, conv, class_embedding, positional, ln_pre, layers, heads, head_dim, eps, owner_id)
+    return _tower_from_rows(rows, B, H // ps, conv, class_embedding, positional, ln_pre, layers, heads, head_dim, eps, owner_id, attn_kernel)
 
 
-def _tower_from_rows(rows, B, grid, conv, class_embedding, positional, ln_pre, layers, heads, head_dim, eps, owner_id) -> torch.Tensor:
+def _tower_from_rows(rows, B, grid, conv, class_embedding, positional, ln_pre, layers, heads, head_dim, eps, owner_id, attn_kernel="fma") -> torch.Tensor:
     D = conv.weight.shape[0]
 
     def build():
@@ -125,7 +142,7 @@ def _tower_from_rows(rows, B, grid, conv, class_embedding, positional, ln_pre, l
     x = assemble_tokens(x, cls, bf16(positional).contiguous())
     x = ops.layernorm(x, bf16(ln_pre.weight), bf16(ln_pre.bias), eps)
     for ln1, w, b, out_proj, ln2, fc1, fc2 in layers:
-        x = prenorm_block(x, heads, ln1, w, b, out_proj, ln2, fc1, fc2, eps=eps, head_dim=head_dim)
+        x = prenorm_block(x, heads, ln1, w, b, out_proj, ln2, fc1, fc2, eps=eps, head_dim=head_dim, attn_kernel=attn_kernel)
     return x
 
 
@@ -146,6 +163,7 @@ class _OCBlock(nn.Module):
 class OpenCLIPVisual(nn.Module):
     """open_clip `VisionTransformer` (the `visual` half of ViT-H-14 / laion2b_s32b_b79k), parameter names as open_clip's: `conv1.weight`, `class_embedding`,
     `positional_embedding`, `ln_pre`, `transformer.resblocks.N.{ln_1, attn.in_proj_weight, attn.in_proj_bias, attn.out_proj, ln_2, mlp.c_fc, mlp.c_proj}`, `ln_post`, `proj`"""
+    attention_kernel = "fma"           # set_attention_kernel
 
     def __init__(self, width=1280, layers=32, heads=16, mlp_ratio=4.0, image_size=224, patch_size=14, output_dim=1024):
         super().__init__()
@@ -168,7 +186,7 @@ class OpenCLIPVisual(nn.Module):
         """every token after the last block, before `ln_post` -- what `encode_with_vision_transformer` returns (condition.py:348-380)"""
         layers = [(r.ln_1, bf16(r.attn.in_proj_weight), bf16(r.attn.in_proj_bias), r.attn.out_proj, r.ln_2, r.mlp.c_fc, r.mlp.c_proj) for r in self.transformer.resblocks]
         return _tower(pixel_values, self.conv1, self.class_embedding, self.positional_embedding, self.ln_pre, layers, self.heads, self.head_dim, self.patch_size_,
-                      self.ln_pre.eps, id(self))
+                      self.ln_pre.eps, id(self), self.attention_kernel)
 
 
 class FrozenOpenCLIPImageEmbedderV2(nn.Module):
@@ -179,6 +197,7 @@ class FrozenOpenCLIPImageEmbedderV2(nn.Module):
     patch-GEMM rows (oracle/kornia_resize_ref.py, parity unpinned).  `preprocess=` overrides it with any callable [b, 3, h, w] -> normalised [b, 3, 224, 224]."""
 
     MEAN, STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
+    attention_kernel = "fma"           # set_attention_kernel (read where `model.visual` carries no mark of its own)
 
     def __init__(self, model=None, preprocess=None, freeze: bool = True, layer: str = "pooled", antialias: bool = True, **config):
         super().__init__()
@@ -205,4 +224,5 @@ class FrozenOpenCLIPImageEmbedderV2(nn.Module):
                                     patch=(1, v.patch_size_, v.patch_size_), mean=self.MEAN, std=self.STD)
         # rows are already the patch-GEMM operand: run the tower from them (same code path as `tokens`, minus the identity pixel pass)
         layers = [(r.ln_1, bf16(r.attn.in_proj_weight), bf16(r.attn.in_proj_bias), r.attn.out_proj, r.ln_2, r.mlp.c_fc, r.mlp.c_proj) for r in v.transformer.resblocks]
-        return _tower_from_rows(rows, B, 224 // v.patch_size_, v.conv1, v.class_embedding, v.positional_embedding, v.ln_pre, layers, v.heads, v.head_dim, v.ln_pre.eps, id(v))
+        return _tower_from_rows(rows, B, 224 // v.patch_size_, v.conv1, v.class_embedding, v.positional_embedding, v.ln_pre, layers, v.heads, v.head_dim, v.ln_pre.eps, id(v),
+                                getattr(v, "attention_kernel", self.attention_kernel))

@@ -6,7 +6,8 @@
 //   attn_varlen.hip     the same tile functions over packed variable-length sequences (mrag_attn_varlen_fwd_bf16; its own parameter block)
 //   attn_tiny.hip       one wavefront per (batch, head) for <= 16 x 16 (temporal attention of the UNets)
 //   attn_fp8.hip        e4m3 operands (mrag_attn_fwd_fp8, mrag_attn_joint_fwd_fp8)
-//   attn_small.hip      other head dims (mrag_attn_small_bf16; its own parameter block)
+//   attn_small.hip      other head dims, short sequences, fp32 FMAs (mrag_attn_small_bf16; its own parameter block)
+//   attn_hd.hip         other head dims at any length on the 32x32x16 MFMA (mrag_attn_hd_fwd_bf16; its own parameter block)
 //   attn_ip_folded.hip  the folded motion-adapter branch (mrag_ip_attn_folded_bf16; scalar arguments, nothing from here but common.h)
 #pragma once
 #include "common.h"

@@ -390,10 +390,11 @@ def attention_1head(x: torch.Tensor, norm: nn.GroupNorm, q, k, v, out) -> torch.
 
 
 def prenorm_block(x: torch.Tensor, heads: int, ln1: nn.LayerNorm, qkv_w: torch.Tensor, qkv_b: Optional[torch.Tensor], out_proj: nn.Linear, ln2: nn.LayerNorm,
-                  fc1: nn.Linear, fc2: nn.Linear, *, eps: float, head_dim: int = 64, mask: Optional[torch.Tensor] = None, ls1=None, ls2=None) -> torch.Tensor:
+                  fc1: nn.Linear, fc2: nn.Linear, *, eps: float, head_dim: int = 64, mask: Optional[torch.Tensor] = None, ls1=None, ls2=None, attn_kernel: str = "fma") -> torch.Tensor:
     """pre-LayerNorm transformer block (VideoMAE, DINOv2, CLIP / open_clip towers): x + [ls1 *] out_proj(attn(ln1(x))), then x + [ls2 *] fc2(gelu(fc1(ln2(x))));
     every residual rides in a GEMM epilogue.  `qkv_w` / `qkv_b`: the fused [3D, D] projection (bf16); `mask`: the head_dim-64 kernel's byte mask;
-    `ls1` / `ls2`: LayerScale modules (`lambda1` [D]), applied through the AdaLN-gate epilogue with a constant gate."""
+    `ls1` / `ls2`: LayerScale modules (`lambda1` [D]), applied through the AdaLN-gate epilogue with a constant gate.  `attn_kernel` (head dims other than 64,
+    clip_vision.set_attention_kernel): "fma" = ops.attention_small wherever it takes the shape, "mfma" = ops.attention_hd everywhere."""
     N, S, D = x.shape
 
     def resid_linear(a, lin, ls, x):
@@ -406,7 +407,9 @@ def prenorm_block(x: torch.Tensor, heads: int, ln1: nn.LayerNorm, qkv_w: torch.T
     if head_dim == 64:
         a = ops.attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], mask=mask)
     elif mask is None:
-        a = ops.attention_small(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2])
+        # what attention_small refuses (K and V of a head beyond its LDS) runs on the MFMA kernel; what it takes stays on it unless the tower opted in
+        hd = attn_kernel == "mfma" or S * head_dim > ops.ATTN_SMALL_MAX_KEY_ELEMS
+        a = (ops.attention_hd if hd else ops.attention_small)(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2])
     else:
         raise NotImplementedError("masked attention at head_dim 64 only")
     x = resid_linear(a, out_proj, ls1, x)

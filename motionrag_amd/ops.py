@@ -420,6 +420,25 @@ KERNEL_TIMING = None
 def attention_small(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """softmax(q k^T * scale) v for short sequences at head dims 32 / 80 / 96 / 128 (mrag_attn_small_bf16): q [B, Sq, H, D], k / v [B, Skv, H, D] with a contiguous
     head dim (views of a fused QKV buffer are fine), Skv * D <= 32 768; out [B, Sq, H * D]"""
+    return _attention_other_dims("mrag_attn_small_bf16", q, k, v, scale, out)
+
+
+ATTN_SMALL_MAX_KEY_ELEMS = 32768    # Skv * D above this: mrag_attn_small_bf16 refuses (K and V of a head no longer fit its 128 KB of LDS)
+
+
+def attn_hd_launch_counts() -> int:
+    """launches of mrag_attn_hd_fwd_bf16 so far (mrag_attn_hd_launch_counts; refused calls do not count)"""
+    return _launch_counts("mrag_attn_hd_launch_counts", 1)[0]
+
+
+def attention_hd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax(q k^T * scale) v on the matrix pipe at head dims 32 / 80 / 96 / 128 and any Sq, Skv (mrag_attn_hd_fwd_bf16): layouts and errors are
+    `attention_small`'s, without its cap on Skv * D"""
+    return _attention_other_dims("mrag_attn_hd_fwd_bf16", q, k, v, scale, out)
+
+
+def _attention_other_dims(entry: str, q, k, v, scale, out) -> torch.Tensor:
+    """one of the two entry points for head dims other than 64: (stream, mrag_attn_args, head_dim)"""
     for n, t in (("q", q), ("k", k), ("v", v)):
         _dev(t, name=n)
         if t.dim() != 4 or t.stride(-1) != 1:
@@ -430,7 +449,7 @@ def attention_small(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, scale:
     a = _attention_views(q, k, v, out)
     a.B, a.H, a.Sq, a.Skv, a.kv_batch_div = B, H, Sq, k.shape[1], 1
     a.scale, a.out_scale = (D ** -0.5) if scale is None else scale, 1.0
-    check(_lib.lib().mrag_attn_small_bf16(_stream(), ctypes.byref(a), D), "mrag_attn_small_bf16")
+    check(getattr(_lib.lib(), entry)(_stream(), ctypes.byref(a), D), entry)
     return out
 
 
