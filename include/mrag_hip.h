@@ -245,6 +245,43 @@ int mrag_gemm_fp8(void* stream, const mrag_gemm_fp8_args* args);
  * whose enumerators are pinned: copies min(n, 2) of them into out_host (HOST memory) and returns 2.  Tests prove with them that the fp8 kernel ran. */
 int mrag_fp8_launch_counts(uint64_t* out_host, int32_t n);
 
+/* ------------------------------------------------------------------------ */
+/* MXFP6 (OCP e2m3, block-scaled) linear -- OPT-IN, a third precision of the  */
+/* same four linears (cogvideox.set_linear_precision(model, "mxfp6")): both   */
+/* operands 6-bit, on the block-scaled MFMA's f6 form (cbsz:2 blgp:2), which  */
+/* gfx950 issues at twice the e4m3 rate.  Nothing takes this path unless asked. */
+/* ------------------------------------------------------------------------ */
+/* The format.  For each row and each block of 32 consecutive k:
+ *   s = the smallest integer with amax * 2^-s <= 7.5 (amax = max |x| of the block), clamped to +-60, 0 for an all-zero block;  scale byte = 127 + s (E8M0);
+ *   element = round-to-nearest-even of the exact value x * 2^-s onto the e2m3 grid +-{0, 0.125 .. 0.875, 1 .. 1.875 in steps of 0.125, 2 .. 3.75 in
+ *   steps of 0.25, 4 .. 7.5 in steps of 0.5}; a tie goes to the even mantissa code; nothing saturates under that scale (a block whose s was clamped
+ *   saturates at +-7.5); a result of zero is +0.  x[m, k] ~ element * 2^s.  Like the e4m3 quantiser this is "the largest scale that fits", not the
+ *   OCP floor rule, so it can be reproduced exactly on the host.
+ * mrag_quant_rows_mxfp6: x [M, K] bf16 with row stride ldx (elements) -> xq, mrag_mxfp6_packed_bytes(M, K) bytes, and scale [M, K / 32] bytes (rows
+ * contiguous).  One pass over x.  The same call quantises nn.Linear weights [N, K].  MRAG_EINVAL for null pointers or M, K < 1; MRAG_ENOTSUP unless
+ * K % 64 == 0, ldx % 8 == 0, ldx >= K and x and xq are 16-byte aligned.                                                                          */
+int mrag_quant_rows_mxfp6(void* stream, const void* x, void* xq, void* scale, int64_t M, int64_t K, int64_t ldx);
+/* The packed operand and its scales back as bf16 y [M, K] (row stride ldy, elements): y[m, k] = element * 2^s, exact in bf16 (four significant bits
+ * times a power of two in range).  Tests and tools read the packed form through this call; it is the only definition of the layout outside the
+ * kernels.  The layout (fragment-major; only this library's kernels produce and consume it): tiles of 32 rows x 64 k, 1536 bytes each, tile (r, c) --
+ * rows 32 r .. 32 r + 31, k 64 c .. 64 c + 63 -- at byte 1536 (r K / 64 + c).  Inside a tile, lane l = (row & 31) + 32 ((k >> 5) & 1) owns 24 bytes:
+ * its bytes 0 .. 15 at 16 l, its bytes 16 .. 23 at 1024 + 8 l; read as a little-endian 192-bit number they hold element k & 31 in bits 6 (k & 31) ..
+ * + 5 as sign | exponent (2 bits, bias 1) | mantissa (3 bits).  Rows M .. 32 ceil(M / 32) - 1 are zeros.  Same return codes as the quantiser.    */
+int mrag_dequant_rows_mxfp6(void* stream, const void* xq, const void* scale, void* y, int64_t M, int64_t K, int64_t ldy);
+/* bytes of the packed operand, 1536 ceil(M / 32) (K / 64), and of its scales, M K / 32; 0 unless M >= 1, K >= 64 and K % 64 == 0 */
+int64_t mrag_mxfp6_packed_bytes(int64_t M, int64_t K);
+int64_t mrag_mxfp6_scale_bytes(int64_t M, int64_t K);
+/* C[m, n] = epilogue( sum_k A[m, k] * W[n, k] + bias[n] ) with A and W as quantised above: fp32 accumulation in ascending 64-deep MFMA steps, the
+ * block scales applied inside the MFMA (E8M0 scale operands: exact).  On the argument block of mrag_gemm_fp8: A8 / W8 name the PACKED operands of
+ * [M, K] / [N, K] (16-byte aligned), a_scale / w_scale their scale bytes [M, K / 32] / [N, K / 32] (4-byte aligned); a_exp, w_exp, lda and ldw are
+ * not read.  Epilogues MRAG_EPI_NONE, MRAG_EPI_GELU_TANH, MRAG_EPI_RESID and MRAG_EPI_GATE_RESID with the semantics, the row-range fields and the
+ * rounding points of mrag_gemm_fp8; C may alias resid.  MRAG_ENOTSUP unless K % 128 == 0 and N % 16 == 0 (any M >= 1) and for every other epilogue;
+ * MRAG_EINVAL for null or misaligned pointers (as mrag_gemm_fp8).  Every check returns before any launch.                                        */
+int mrag_gemm_mxfp6(void* stream, const mrag_gemm_fp8_args* args, const void* a_scale, const void* w_scale);
+/* host-side relaxed launch counters in the form of mrag_fp8_launch_counts: slot 0 mrag_gemm_mxfp6 launches, slot 1 mrag_quant_rows_mxfp6, slot 2
+ * mrag_dequant_rows_mxfp6 (not their refusals).  Copies min(n, 3) slots into out_host (HOST memory), returns 3.                                  */
+int mrag_mxfp6_launch_counts(uint64_t* out_host, int32_t n);
+
 /* The UNets' feed-forward linears on the same path -- OPT-IN (layers.set_ff_precision): the GEGLU projection and the output projection of the
  * DynamiCrafter / SVD transformer blocks' FeedForward (lvdm attention.py:448-475, diffusers FeedForward), whose level-0 width K = 320 is 2.5 K-tiles.
  *

@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libmrag_hip.so")
 # compiled in this order, at most MAX_COMPILERS at a time: the long units first, so that none of them starts late behind the short ones
-SOURCES = ["gemm_tiled.hip", "gemm_w4.hip", "topk_scan.hip", "gemm_conv.hip", "attn16.hip", "topk_dense.hip", "topk_mfma.hip", "attn_flash.hip", "attn_varlen.hip", "gemm_skinny.hip", "gemm_fp8.hip", "ff_fused.hip", "conv_fp8.hip", "api.hip", "gemm_bf16.hip", "gemm_k320.hip", "attn_fp8.hip",
+SOURCES = ["gemm_tiled.hip", "gemm_w4.hip", "topk_scan.hip", "gemm_conv.hip", "attn16.hip", "topk_dense.hip", "topk_mfma.hip", "attn_flash.hip", "attn_varlen.hip", "gemm_skinny.hip", "gemm_fp8.hip", "gemm_mxfp6.hip", "ff_fused.hip", "conv_fp8.hip", "api.hip", "gemm_bf16.hip", "gemm_k320.hip", "attn_fp8.hip",
            "comm.hip", "norm.hip", "pointwise.hip", "preprocess.hip", "unet_ops.hip", "cama_seq.hip", "attn_ip_folded.hip", "attn_bf16.hip", "attn_hd.hip", "attn_small.hip", "attn_tiny.hip", "topk.hip", "probe.hip"]
 MAX_COMPILERS = 16
 ABI_VERSION = 11

@@ -87,7 +87,7 @@ def _joint_sdpa(q, k, v, fp8_attn: bool):
 
 
 def joint_attention_core(attn, proc, x: torch.Tensor, text_len: int, rope, ip_hidden_states: Optional[torch.Tensor], scale: float, sp=None,
-                         fp8_qkv: bool = False, fp8_attn: bool = False):
+                         fp8_qkv: bool = False, fp8_attn: bool = False, mxfp6_qkv: bool = False):
     """attn_processor.py:209-273 on the joint [text ; video] sequence x [B, S, D] (bf16, contiguous).
     Returns the attention output BEFORE to_out: `o + scale * ip_attention(to_q_ip(o))`.
     `sp` (dist.SequenceParallel): x holds only this rank's rows (text_len / rope already local); K and V rows of all ranks are
@@ -95,7 +95,8 @@ def joint_attention_core(attn, proc, x: torch.Tensor, text_len: int, rope, ip_hi
     `fp8_qkv` (cogvideox.set_linear_precision): the fused QKV projection on the e4m3 GEMM, then the stand-alone qk-norm + RoPE kernel; ignored
     under `sp` (the sharded projection's [K | V]-first order lives in the bf16 GEMM's fused epilogue).
     `fp8_attn` (cogvideox.set_attention_precision): the joint attention itself on the e4m3 kernel (ops.joint_attention_fp8), on every path, sharded included;
-    independent of `fp8_qkv`.  The motion branch stays bf16."""
+    independent of `fp8_qkv`.  The motion branch stays bf16.
+    `mxfp6_qkv` (cogvideox.set_linear_precision(model, "mxfp6")): as `fp8_qkv`, on the MXFP6 GEMM (ops.linear_mxfp6); ignored under `sp` likewise."""
     B, S, D = x.shape
     H = attn.heads
     fw = proc._fused
@@ -113,11 +114,15 @@ def joint_attention_core(attn, proc, x: torch.Tensor, text_len: int, rope, ip_hi
     if sp is not None:
         o = _sharded_attention(attn, x, wqkv, bqkv, H, nq, nk, cos, sin, text_len, sp, fp8_attn)
         return _motion_branch(attn, proc, o, ip_hidden_states, scale)
-    if fp8_qkv:
-        # the concatenated weight quantised once per output channel; the projection with a plain epilogue, then norm_q / norm_k + RoPE in place
-        # (the two-kernel form ops.qkv_linear_qknorm_rope falls back to)
-        w8, w_exp = fw.get("qkv8", tuple(m.weight for m in qkv_lins), lambda: ops.quant_rows_e4m3(wqkv))
-        qkv = ops.linear_fp8(x, w8, w_exp, bqkv)
+    if fp8_qkv or mxfp6_qkv:
+        # the concatenated weight quantised once (e4m3: per output channel; MXFP6: per block of 32); the projection with a plain epilogue, then
+        # norm_q / norm_k + RoPE in place (the two-kernel form ops.qkv_linear_qknorm_rope falls back to)
+        if fp8_qkv:
+            w8, w_exp = fw.get("qkv8", tuple(m.weight for m in qkv_lins), lambda: ops.quant_rows_e4m3(wqkv))
+            qkv = ops.linear_fp8(x, w8, w_exp, bqkv)
+        else:
+            wq, w_scale = fw.get("qkv6", tuple(m.weight for m in qkv_lins), lambda: ops.quant_rows_mxfp6(wqkv))
+            qkv = ops.linear_mxfp6(x, wq, w_scale, bqkv)
         ops.qknorm_rope_(qkv, H, nq.weight if nq is not None else None, nq.bias if nq is not None else None, nk.weight if nk is not None else None,
                          nk.bias if nk is not None else None, cos, sin, text_len, eps=nq.eps if nq is not None else 1e-6, q_premul=ops.LOG2E * 64 ** -0.5)
         q5 = qkv.view(B, S, 3, H, 64)

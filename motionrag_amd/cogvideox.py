@@ -101,15 +101,19 @@ def set_linear_precision(model: "CogVideoXTransformer3DModel", precision: str = 
     """'bf16' (the reference's precision: every call exactly where it is without this option) or 'fp8': the named sites of every CogVideoXBlock --
     "qkv" (to_q / to_k / to_v, attn_processor.py:209-211), "to_out" (:276), "ff1" / "ff2" (diffusers FeedForward) -- run on the e4m3 GEMM
     (ops.linear_fp8): activations quantised per row in front of each GEMM, weights per output channel, lazily and once.  Under sequence sharding
-    the QKV projection stays bf16.  The motion branch, the embeddings, the modulation GEMM and proj_out are bf16 either way."""
-    if precision not in ("bf16", "fp8"):
-        raise ValueError("precision must be 'bf16' or 'fp8'")
+    the QKV projection stays bf16.  The motion branch, the embeddings, the modulation GEMM and proj_out are bf16 either way.
+    'mxfp6': the same sites on the MXFP6 GEMM (ops.linear_mxfp6): both operands OCP e2m3 with one power-of-two scale per block of 32 along K
+    (include/mrag_hip.h states the format), activations quantised in front of each GEMM, weights lazily and once; the same exceptions.  The sites
+    then stand in `model.linear_mxfp6_sites`; `model.linear_fp8_sites` is empty unless the precision is 'fp8'."""
+    if precision not in ("bf16", "fp8", "mxfp6"):
+        raise ValueError("precision must be 'bf16', 'fp8' or 'mxfp6'")
     sites = tuple(sites)
     bad = [s for s in sites if s not in LINEAR_SITES]
     if bad:
         raise ValueError(f"unknown linear site(s) {bad}: choose from {LINEAR_SITES}")
     model.linear_precision = precision
     model.linear_fp8_sites = frozenset(sites) if precision == "fp8" else frozenset()
+    model.linear_mxfp6_sites = frozenset(sites) if precision == "mxfp6" else frozenset()
     return model
 
 
@@ -128,6 +132,7 @@ class CogVideoXTransformer3DModel(nn.Module):
     """CogVideoX-5B-I2V DiT (rotary + learned positional embedding flavour)."""
     linear_precision = "bf16"          # set_linear_precision
     linear_fp8_sites = frozenset()
+    linear_mxfp6_sites = frozenset()
     attention_precision = "bf16"       # set_attention_precision
 
     def __init__(self, num_layers=42, num_attention_heads=48, attention_head_dim=64, in_channels=32, out_channels=16, time_embed_dim=512,
@@ -150,7 +155,8 @@ class CogVideoXTransformer3DModel(nn.Module):
         self.norm_final = nn.LayerNorm(D, eps=norm_eps)
         self.norm_out = _AdaLayerNorm(time_embed_dim, D, norm_eps)
         self.proj_out = nn.Linear(D, patch_size * patch_size * out_channels)
-        # "mod" / "patch_w" (below) and (site, layer) -> the weight's e4m3 rows + exponents (set_linear_precision)
+        # "mod" / "patch_w" (below) and (site, layer) -> the weight's e4m3 rows + exponents, (site, layer, "mxfp6") -> its packed e2m3 form + block
+        # scales (set_linear_precision)
         self._fused = WeightCache()
         self._plain = _PlainProcessor()
 
@@ -254,10 +260,13 @@ class CogVideoXTransformer3DModel(nn.Module):
             off = (layer_slot * 6 + j) * D
             return mod[:, off:off + D]
 
-        fp8 = self.linear_fp8_sites
+        fp8, mx6 = self.linear_fp8_sites, self.linear_mxfp6_sites
 
         def site_linear(site: str, layer: int, inp: torch.Tensor, lin: nn.Linear, **kw) -> torch.Tensor:
             """one of the block's large linears in the precision its site is set to"""
+            if site in mx6:
+                wq, w_scale = self._fused.get((site, layer, "mxfp6"), lin.weight, lambda: ops.quant_rows_mxfp6(lin.weight.detach()))
+                return ops.linear_mxfp6(inp, wq, w_scale, lin.bias, **kw)
             if site not in fp8:
                 return ops.linear(inp, lin.weight, lin.bias, **kw)
             w8, w_exp = self._fused.get((site, layer), lin.weight, lambda: ops.quant_rows_e4m3(lin.weight.detach()))
@@ -269,7 +278,8 @@ class CogVideoXTransformer3DModel(nn.Module):
             nh = ops.layernorm(x, blk.norm1.norm.weight, blk.norm1.norm.bias, cfg["norm_eps"], shift0=chunk(2 * i, 3), scale0=chunk(2 * i, 4),
                                shift1=chunk(2 * i, 0), scale1=chunk(2 * i, 1), rows_per_batch=S, split=Lt, mod_stride=ms)
             scale = proc.scale[0] if ip is not None else 0.0
-            o = joint_attention_core(blk.attn1, proc, nh, Lt, rope, ip, scale, sp=sp, fp8_qkv="qkv" in fp8, fp8_attn=self.attention_precision == "fp8")
+            o = joint_attention_core(blk.attn1, proc, nh, Lt, rope, ip, scale, sp=sp, fp8_qkv="qkv" in fp8, fp8_attn=self.attention_precision == "fp8",
+                                     mxfp6_qkv="qkv" in mx6)
             site_linear("to_out", i, o, blk.attn1.to_out[0], out=x, epilogue=ops.EPI_GATE_RESID, resid=x,
                         gate0=chunk(2 * i, 5), gate1=chunk(2 * i, 2), rows_per_batch=S, split=Lt, gate_stride=ms)
             nh = ops.layernorm(x, blk.norm2.norm.weight, blk.norm2.norm.bias, cfg["norm_eps"], shift0=chunk(2 * i + 1, 3),

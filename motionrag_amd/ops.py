@@ -623,6 +623,106 @@ def linear_fp8(x: torch.Tensor, w8: torch.Tensor, w_exp: torch.Tensor, bias: Opt
     return out
 
 
+def mxfp6_launch_counts() -> dict:
+    """launches of the MXFP6 linear path's three entry points so far (mrag_mxfp6_launch_counts): {"gemm": n, "quant": n, "dequant": n}"""
+    return dict(zip(("gemm", "quant", "dequant"), _launch_counts("mrag_mxfp6_launch_counts", 3)))
+
+
+def mxfp6_linear_supported(N: int, K: int) -> bool:
+    """shapes mrag_gemm_mxfp6 takes (include/mrag_hip.h): whole 128-deep K-tiles, 16-byte aligned output rows; any row count"""
+    return N > 0 and K > 0 and K % 128 == 0 and N % 16 == 0
+
+
+def _mxfp6_sizes(M: int, K: int):
+    """(packed bytes, scale bytes) of an [M, K] operand, from the library's size queries"""
+    L = _lib.lib()
+    return int(L.mrag_mxfp6_packed_bytes(M, K)), int(L.mrag_mxfp6_scale_bytes(M, K))
+
+
+def quant_rows_mxfp6(x: torch.Tensor, out: Optional[tuple] = None):
+    """block-scaled e2m3 copy of x [..., K] bf16 (mrag_quant_rows_mxfp6; the format is stated in include/mrag_hip.h): returns (xq, scale) with xq a
+    flat uint8 tensor of mrag_mxfp6_packed_bytes(M, K) bytes in the library's packed layout (read it with `dequant_rows_mxfp6`) and scale [M, K / 32]
+    uint8, the E8M0 byte 127 + s of each block of 32.  `out` = (xq, scale) buffers to fill.  The same call quantises nn.Linear weights [N, K]."""
+    _dev(x, name="x")
+    x2 = _rows(x)
+    M, K = x2.shape
+    if K % 64 != 0 or x2.stride(0) % 8 != 0 or x2.data_ptr() % 16 != 0:
+        raise ValueError(f"quant_rows_mxfp6: K % 64 == 0 and 16-byte aligned rows (got K={K}, row stride {x2.stride(0)})")
+    nq, ns = _mxfp6_sizes(M, K)
+    if out is None:
+        out = (torch.empty(nq, dtype=torch.uint8, device=x.device), torch.empty(M, K // 32, dtype=torch.uint8, device=x.device))
+    xq, sc = out
+    _dev(xq, torch.uint8, "xq"); _dev(sc, torch.uint8, "scale")
+    if xq.dim() != 1 or xq.numel() != nq or not xq.is_contiguous() or tuple(sc.shape) != (M, K // 32) or not sc.is_contiguous() or xq.data_ptr() % 16 != 0:
+        raise ValueError(f"quant_rows_mxfp6: out = (xq [{nq}] uint8, 16-byte aligned; scale [M, K / 32] uint8, contiguous)")
+    check(_lib.lib().mrag_quant_rows_mxfp6(_stream(), _p(x2), _p(xq), _p(sc), M, K, x2.stride(0)), "mrag_quant_rows_mxfp6")
+    return xq, sc
+
+
+def dequant_rows_mxfp6(xq: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(xq, scale) of `quant_rows_mxfp6` back as bf16 [M, K] (mrag_dequant_rows_mxfp6): exactly element * 2^s.  How tests and tools read the packed form."""
+    _dev(xq, torch.uint8, "xq"); _dev(scale, torch.uint8, "scale")
+    if scale.dim() != 2 or not scale.is_contiguous():
+        raise ValueError("dequant_rows_mxfp6: scale [M, K / 32] uint8, contiguous")
+    M, K = scale.shape[0], scale.shape[1] * 32
+    nq, _ = _mxfp6_sizes(M, K)
+    if K % 64 != 0 or xq.dim() != 1 or xq.numel() != nq or not xq.is_contiguous() or xq.data_ptr() % 16 != 0:
+        raise ValueError(f"dequant_rows_mxfp6: xq must be the {nq} packed bytes of a [{M}, {K}] operand (K % 64 == 0)")
+    if out is None:
+        out = torch.empty(M, K, dtype=torch.bfloat16, device=xq.device)
+    _dev(out, name="out")
+    if tuple(out.shape) != (M, K) or out.stride(1) != 1 or out.stride(0) % 8 != 0 or out.data_ptr() % 16 != 0:
+        raise ValueError("dequant_rows_mxfp6: out [M, K] bf16 with 16-byte aligned rows")
+    check(_lib.lib().mrag_dequant_rows_mxfp6(_stream(), _p(xq), _p(scale), _p(out), M, K, out.stride(0)), "mrag_dequant_rows_mxfp6")
+    return out
+
+
+def _mxfp6_rows_workspace(device: torch.device, M: int, K: int):
+    """(xq, scale [M, K / 32]) inside the grow-only workspace "mxfp6lin" of the (device, stream)"""
+    nq, ns = _mxfp6_sizes(M, K)
+    sc_bytes = (ns + 255) // 256 * 256
+    ws = _attn_workspace(device, sc_bytes + nq, "mxfp6lin")
+    return ws[sc_bytes:sc_bytes + nq], ws[:ns].view(M, K // 32)
+
+
+def linear_mxfp6(x: torch.Tensor, wq: torch.Tensor, w_scale: torch.Tensor, bias: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None,
+                 epilogue: int = EPI_NONE, resid: Optional[torch.Tensor] = None, gate0: Optional[torch.Tensor] = None,
+                 gate1: Optional[torch.Tensor] = None, rows_per_batch: int = 0, split: int = 0, gate_stride: int = 0) -> torch.Tensor:
+    """out = epilogue(x @ W.T + bias) on the MXFP6 MFMA path: x [..., K] bf16 is quantised per block of 32 into a grow-only workspace of the
+    (device, stream), (wq, w_scale) = quant_rows_mxfp6(weight) is the weight quantised once.  Epilogues EPI_NONE / EPI_GELU_TANH / EPI_RESID /
+    EPI_GATE_RESID as in `linear_fp8` (out may be resid).  Two launches, nothing read back: capturable into a HIP graph.  Raises on shapes the kernel
+    does not take (`mxfp6_linear_supported`): opting in is explicit, so is its refusal."""
+    x2 = _rows(_dev(x, name="x"))
+    M, K = x2.shape
+    _dev(wq, torch.uint8, "wq"); _dev(w_scale, torch.uint8, "w_scale")
+    if bias is not None:
+        _dev(bias, name="bias")
+    if w_scale.dim() != 2 or w_scale.shape[1] * 32 != K or not w_scale.is_contiguous():
+        raise ValueError(f"linear_mxfp6: w_scale {tuple(w_scale.shape)} does not match K={K}")
+    N = w_scale.shape[0]
+    if not mxfp6_linear_supported(N, K):
+        raise ValueError(f"linear_mxfp6: N={N}, K={K} outside the MXFP6 GEMM's shapes (K % 128 == 0, N % 16 == 0)")
+    if wq.dim() != 1 or wq.numel() != _mxfp6_sizes(N, K)[0] or not wq.is_contiguous():
+        raise ValueError(f"linear_mxfp6: wq is not the packed form of a [{N}, {K}] weight")
+    if epilogue not in (EPI_NONE, EPI_GELU_TANH, EPI_RESID, EPI_GATE_RESID):
+        raise ValueError(f"linear_mxfp6: epilogue {epilogue} does not exist on the MXFP6 GEMM")
+    aq, a_scale = _mxfp6_rows_workspace(x.device, M, K)
+    quant_rows_mxfp6(x2, out=(aq, a_scale))
+    if out is None:
+        out = torch.empty(*x.shape[:-1], N, dtype=torch.bfloat16, device=x.device)
+    o2 = _rows(_dev(out, name="out"))
+    a = GemmFp8Args()
+    a.A8, a.W8, a.bias, a.C, a.M, a.N, a.K, a.ldc, a.epilogue = _p(aq), _p(wq), _p(bias), _p(o2), M, N, K, o2.stride(0), epilogue
+    if resid is not None:
+        r2 = _rows(_dev(resid, name="resid"))
+        a.resid, a.ldr = _p(r2), r2.stride(0)
+    if epilogue == EPI_GATE_RESID:
+        a.gate0, a.gate1 = _p(_dev(gate0, name="gate0")), _p(_dev(gate1, name="gate1"))
+        a.rows_per_batch, a.split, a.gate_stride = rows_per_batch, split, gate_stride
+    check(_lib.lib().mrag_gemm_mxfp6(_stream(), ctypes.byref(a), _p(a_scale), _p(w_scale)), "mrag_gemm_mxfp6")
+    return out
+
+
 def fp8_k64_launch_counts() -> dict:
     """launches of the feed-forward fp8 path's two entry points so far (mrag_gemm_fp8_k64_launch_counts): {"gemm": n, "ln": n}"""
     return dict(zip(("gemm", "ln"), _launch_counts("mrag_gemm_fp8_k64_launch_counts", 2)))
